@@ -9,10 +9,13 @@ with its inputs already resident in HBM (flatten + upload happen before the time
 maxmin_bench.cpp:81-83 times only solve()).  With --gpus N every rank solves its own independent
 system (seed = rank + 1): a parameter sweep, weak scaling, no data-path collective.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with a `roofline` object for the
-dominant kernel (HIP events on the solver's own stream, per-launch algorithmic bytes from the
-per-round work profile) and a `cpu_baseline` object (the oracle, single-threaded, on a bounded
-1/10-scale sample of the same generator).
+Prints ONE JSON line on rank 0.  A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the
+headline figure needs: build, warm up, time the N steps, write the outputs if --dump-outputs is given, print
+the line (its `roofline` object holds the solve-level figures, which need no run of their own).  With --full
+the line also carries what takes further runs: the dominant kernel's roofline (one profiled solve: HIP events
+on the solver's own stream, per-launch algorithmic bytes from the per-round work profile), the drop-in
+`System::solve()` steps and a `cpu_baseline` object (the oracle, single-threaded, on a bounded 1/10-scale
+sample of the same generator, with the GPU-vs-oracle parity of that sample).
 """
 import argparse
 import json
@@ -145,6 +148,23 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+DUMP_MAX_VALUES = 4_000_000  # 32 MB of float64 per array
+
+
+def dump_outputs(dirname, rank, world, arrays):
+    """--dump-outputs: what the timed path computed in its last step, one <name>.npy (float64) per array (per rank
+    <name>_rank<r>.npy when there are several).  An array longer than DUMP_MAX_VALUES is cut to a fixed, seeded
+    sample of its entries, kept in index order: the same entries in every run and every build."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    for name, x in arrays.items():
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.size > DUMP_MAX_VALUES:
+            x = x[np.sort(np.random.default_rng(20261019).choice(x.size, DUMP_MAX_VALUES, replace=False))]
+        np.save(os.path.join(dirname, name + ("" if world == 1 else f"_rank{rank}") + ".npy"), x)
+
+
 def host_info():
     """CPU model and core counts of the box the CPU baseline ran on."""
     model = None
@@ -204,9 +224,16 @@ def main():
     ap.add_argument("--cnst", type=int, default=1_000_000)
     ap.add_argument("--vars", type=int, default=10_000_000)
     ap.add_argument("--k", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the profiled solve (dominant-kernel"
+                         " roofline), the drop-in System::solve() steps (c2), the CPU baseline and its parity check")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the variable values of the last timed solve (dense order) to"
+                         " DIR/values.npy (float64; a fixed seeded sample of 4e6 entries when there are more)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-sample-div", type=int, default=10, help="CPU baseline sample = 1/div of the workload")
-    ap.add_argument("--profile-json", default=None, help="write the per-launch profile here")
+    ap.add_argument("--profile-json", default=None,
+                    help="run the profiled solve (as --full does) and write its per-launch profile here")
     ap.add_argument("--workload", default="c2", choices=["c2", "c3", "c4", "c5"],
                     help="c2 = the BASELINE metric's config (default); c3/c4/c5 = the other SURVEY.md §8(d) configs")
     ap.add_argument("--flows", type=int, default=None, help="c4/c5: number of flows (default 1e5 / 1e7)")
@@ -215,8 +242,9 @@ def main():
     ap.add_argument("--variant", default="plain", choices=["plain", "stress"],
                     help="c2: stress = 5%% FATPIPE constraints, 10%% bounded variables, penalties {1,2,4}")
     ap.add_argument("--dropin-steps", type=int, default=3,
-                    help="c2: System::solve() steps through the public API after the timed region (0 = skip)")
-    ap.add_argument("--cpu-reps", type=int, default=3, help="CPU baseline repetitions (mean and sd reported)")
+                    help="c2, --full: System::solve() steps through the public API after the timed region (0 = skip)")
+    ap.add_argument("--cpu-reps", type=int, default=3,
+                    help="--full: CPU baseline repetitions (mean and sd reported)")
     ap.add_argument("--cpu-worker", nargs=3, metavar=("WORKLOAD", "LO", "HI"), default=None,
                     help=argparse.SUPPRESS)  # child process of the N-process CPU baseline
     args = ap.parse_args()
@@ -250,7 +278,8 @@ def main():
     t = time.time()
     s = lmm.System(False)
     gen_kw = STRESS_KW if args.variant == "stress" else {}
-    vs = s.gen_synthetic(args.cnst, args.vars, args.k, seed=rank + 1, want_vars=args.dropin_steps > 0, **gen_kw)
+    dropin_steps = args.dropin_steps if args.full else 0
+    vs = s.gen_synthetic(args.cnst, args.vars, args.k, seed=rank + 1, want_vars=dropin_steps > 0, **gen_kw)
     t_gen = time.time() - t
     t = time.time()
     s.prepare()  # flatten + upload: inputs resident in HBM from here on
@@ -274,61 +303,27 @@ def main():
     n_vars_total = args.vars * world * args.steps
     value = n_vars_total / elapsed
     ms_per_step = 1000.0 * elapsed / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, {"values": s.device_values()})
 
-    # ---- profiled solve: per-launch HIP events on the solver's stream + per-round work ----
-    s.set_profiling(True)
-    s.device_solve()
-    s.set_profiling(False)
-    slot, rnd, ms = s.launch_profile()
-    av, ae = s.round_profile()
-    rv, re_ = s.vote_profile()
     nV, nC, nnz, rounds = st["n_var"], st["n_cnst"], st["nnz"], st["rounds"]
-    per_kernel = {}
-    for k in sorted(set(slot.tolist())):
-        sel = slot == k
-        byts = 0
-        for r in rnd[sel]:
-            if 0 <= r < len(av):
-                nxt_v = int(av[r + 1]) if r + 1 < len(av) else 0
-                nxt_e = int(ae[r + 1]) if r + 1 < len(ae) else 0
-                rr = (int(rv[r]), int(re_[r])) if r < len(rv) else (0, 0)
-                byts += kernel_bytes(int(k), nV, nC, int(av[r]), int(ae[r]), int(av[r]) - nxt_v,
-                                     int(ae[r]) - nxt_e, *rr)
-            elif r < 0:
-                byts += kernel_bytes(int(k), nV, nC, nV, nnz, 0, 0, 0, 0)
-        per_kernel[SLOT_NAMES[int(k)]] = dict(launches=int(sel.sum()), total_ms=float(ms[sel].sum()),
-                                              avg_us=float(1000 * ms[sel].mean()), alg_bytes=int(byts))
-    dom = max(per_kernel, key=lambda n: per_kernel[n]["total_ms"])
-    d = per_kernel[dom]
-    kach = d["alg_bytes"] / (d["total_ms"] * 1e-3) / 1e9
     solve_alg = 56 * nnz + 24 * nV + 32 * nC
     roofline = roofline_obj(solve_alg * world, ms_per_step, "c2" if args.variant == "plain" else "c2_stress",
                             "SURVEY.md §8(d) lmm_solve: 56 nnz + 24 V + 32 C bytes per solve (x ranks)", gpus=world)
     if world == 1 and args.variant == "plain":
         roofline["requests"] = request_roofline("c2", ms_per_step)
-    # secondary: the dominant kernel's own per-launch byte model (kernel_bytes) over its HIP-event time
-    roofline["dominant_kernel"] = {"name": dom, "avg_us": round(d["avg_us"], 2), "launches": d["launches"],
-                                   "alg_bytes_per_launch": int(d["alg_bytes"] / max(1, d["launches"])),
-                                   "achieved_gbs": round(kach, 1), "kernel_frac": round(kach / HBM_PEAK_GBS, 4)}
-    if args.profile_json and rank == 0:
-        extra = {}
-        if os.environ.get("LMMHIP_VOTE_DIAG"):
-            extra["vote_diag"] = s.vote_diag_profile().tolist()
-        with open(args.profile_json, "w") as f:
-            json.dump(dict(per_kernel=per_kernel, rounds=rounds, alive_vars=av.tolist(), alive_elems=ae.tolist(), **extra,
-                           reeval_vars=rv.tolist(), reeval_elems=re_.tolist(),
-                           device_ms=st["device_ms"], launch_slot=slot.tolist(), launch_round=rnd.tolist(),
-                           launch_ms=ms.tolist()), f)
+    if args.full or args.profile_json:
+        profiled_solve(s, st, roofline, args, rank)
 
     # ---- drop-in step: System::solve() through the public API after simulation-side mutations ----
     # Each step first changes 1e4 variable penalties and 1e3 constraint bounds through the API (untimed: the
     # simulation's own work), then times solve() = delta-log ship + device flatten or refresh + device solve
     # + value scatter into the host System (resident mode, the default).
     dropin = None
-    if args.dropin_steps > 0:
+    if dropin_steps > 0:
         rng = np.random.default_rng(9 + rank)
         rows = []
-        for _ in range(args.dropin_steps):
+        for _ in range(dropin_steps):
             for i in rng.choice(args.vars, 10_000, replace=False):
                 s.update_variable_penalty(lmm.Variable(s, int(vs[i])), float(rng.choice([0.5, 1.0, 2.0])))
             for c in rng.choice(args.cnst, 1_000, replace=False):
@@ -341,14 +336,14 @@ def main():
         med = np.median(np.array(rows), axis=0)
         dropin = {"solve_step_ms": round(float(med[0]), 2), "host_ms": round(float(med[1]), 2),
                   "ship_and_device_flatten_ms": round(float(med[2]), 2), "device_solve_ms": round(float(med[3]), 2),
-                  "value_scatter_ms": round(float(med[4]), 2), "steps": args.dropin_steps,
+                  "value_scatter_ms": round(float(med[4]), 2), "steps": dropin_steps,
                   "vars_per_s": round(args.vars / (float(med[0]) * 1e-3), 1),
                   "mutations_per_step": "1e4 penalty + 1e3 constraint-bound updates (untimed)",
                   "path": "System::solve(), resident mode (default): median over the steps"}
 
     # ---- CPU baseline: the oracle (single-threaded restatement), bounded sample, rank 0, N=1 ----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import pyoracle as O
 
         div = args.cpu_sample_div
@@ -391,6 +386,49 @@ def main():
     del s  # free the device context while the HIP runtime is up (not in interpreter teardown)
     if dist is not None:
         dist.destroy_process_group()
+
+
+def profiled_solve(s, st, roofline, args, rank):
+    """One more solve with per-launch HIP events on the solver's stream and the per-round work profile: the
+    dominant kernel's own roofline (into `roofline`) and, with --profile-json, the per-launch profile."""
+    s.set_profiling(True)
+    s.device_solve()
+    s.set_profiling(False)
+    slot, rnd, ms = s.launch_profile()
+    av, ae = s.round_profile()
+    rv, re_ = s.vote_profile()
+    nV, nC, nnz, rounds = st["n_var"], st["n_cnst"], st["nnz"], st["rounds"]
+    per_kernel = {}
+    for k in sorted(set(slot.tolist())):
+        sel = slot == k
+        byts = 0
+        for r in rnd[sel]:
+            if 0 <= r < len(av):
+                nxt_v = int(av[r + 1]) if r + 1 < len(av) else 0
+                nxt_e = int(ae[r + 1]) if r + 1 < len(ae) else 0
+                rr = (int(rv[r]), int(re_[r])) if r < len(rv) else (0, 0)
+                byts += kernel_bytes(int(k), nV, nC, int(av[r]), int(ae[r]), int(av[r]) - nxt_v,
+                                     int(ae[r]) - nxt_e, *rr)
+            elif r < 0:
+                byts += kernel_bytes(int(k), nV, nC, nV, nnz, 0, 0, 0, 0)
+        per_kernel[SLOT_NAMES[int(k)]] = dict(launches=int(sel.sum()), total_ms=float(ms[sel].sum()),
+                                              avg_us=float(1000 * ms[sel].mean()), alg_bytes=int(byts))
+    dom = max(per_kernel, key=lambda n: per_kernel[n]["total_ms"])
+    d = per_kernel[dom]
+    kach = d["alg_bytes"] / (d["total_ms"] * 1e-3) / 1e9
+    # secondary: the dominant kernel's own per-launch byte model (kernel_bytes) over its HIP-event time
+    roofline["dominant_kernel"] = {"name": dom, "avg_us": round(d["avg_us"], 2), "launches": d["launches"],
+                                   "alg_bytes_per_launch": int(d["alg_bytes"] / max(1, d["launches"])),
+                                   "achieved_gbs": round(kach, 1), "kernel_frac": round(kach / HBM_PEAK_GBS, 4)}
+    if args.profile_json and rank == 0:
+        extra = {}
+        if os.environ.get("LMMHIP_VOTE_DIAG"):
+            extra["vote_diag"] = s.vote_diag_profile().tolist()
+        with open(args.profile_json, "w") as f:
+            json.dump(dict(per_kernel=per_kernel, rounds=rounds, alive_vars=av.tolist(), alive_elems=ae.tolist(), **extra,
+                           reeval_vars=rv.tolist(), reeval_elems=re_.tolist(),
+                           device_ms=st["device_ms"], launch_slot=slot.tolist(), launch_round=rnd.tolist(),
+                           launch_ms=ms.tolist()), f)
 
 
 def c2_full_size_baseline(args, gpu_value):
@@ -659,6 +697,9 @@ def run_config(args):
         if args.workload == "c5":
             work = ex.sum(work)
     ms_per_step = 1000.0 * elapsed / args.steps
+    if args.dump_outputs:  # dense order: c3 the systems concatenated, c5 at N > 1 this rank's variables
+        x = batch.values() if batch is not None else shards[0].values() if shards is not None else s.device_values()
+        dump_outputs(args.dump_outputs, rank, world, {"values": x})
     # algorithmic bytes of one solve: maxmin 56 B/element + 24 B/variable + 32 B/constraint;
     # fair bottleneck sum over the rounds of 36 B/element + 32 B/variable + 32 B/constraint of the listed ones
     if args.workload == "c5":
@@ -682,7 +723,7 @@ def run_config(args):
                            device_ms=s.last_stats()["device_ms"], launch_slot=slot.tolist(),
                            launch_round=rnd.tolist(), launch_ms=ms.tolist()), f)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = config_cpu_baseline(args.workload, args.flows, args.cpu_reps)
     roof = roofline_obj(alg, ms_per_step, args.workload, note, gpus=world)
     if world == 1 and args.workload in ("c4", "c5"):  # the request-rate roofline of the solve (VERDICT r05 Next #5)
