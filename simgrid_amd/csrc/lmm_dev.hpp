@@ -206,6 +206,66 @@ struct Dev {
 __device__ __forceinline__ int rvar(int32_t cv) { return cv & 0x7FFFFFFF; }
 __device__ __forceinline__ bool rbounded(int32_t cv) { return cv < 0; }
 
+// Resident mirror (lmm_resident_kernels.hpp; host ids; capacities grow on demand, contents survive growth).
+struct ResDev {
+  int32_t* e_cnst;   // [capE] constraint of element slot e
+  double* e_w;       // [capE] consumption weight
+  uint8_t* e_fl;     // [capE] bit0: in its constraint's enabled list
+  int64_t* v_ebase;  // [capV] first element slot of the variable's slab
+  int32_t* v_n;      // [capV] elements in use; -1 = dead variable (lmm_system.cpp; loops `i < n` skip it, rs_apply_v validates it)
+  double* v_pen;     // [capV] sharing penalty
+  double* v_bound;   // [capV] bound (-1 = none)
+  double* c_bound;   // [capC]
+  uint8_t* c_fl;     // [capC] bit0: FATPIPE
+};
+
+// Sharded FairBottleneck: the constraints a shard owns (lmm_fb_kernels.hpp, fbo_*).
+struct FbOwner {
+  int32_t nc;             // owned constraints
+  int32_t nch;            // their chunks (kFbChunk elements)
+  int64_t mu_off;         // position of this shard's first variable in xmu
+  const int32_t* oc;      // [nc] global id of each owned constraint
+  const uint32_t* optr;   // [nc+1] element offsets
+  const int32_t* ovar;    // [onnz] position of the element's variable in xmu
+  const double* ow;       // [onnz] weight
+  const int32_t* och_o;   // [nch] owned-constraint index of each chunk
+  const uint32_t* och_b;  // [nch] first element of each chunk
+  const int32_t* cpos;    // [nC] position of each constraint's remaining in xrem
+  double* fbd;            // [onnz] increments w * mu (owned CSC order)
+  double* xmu;            // gathered mu (caller's buffer)
+  double* xrem;           // gathered remaining (caller's buffer)
+};
+
+// Model-side action state (lmm_step_kernels.hpp).
+struct ActDev {
+  int64_t n;
+  const int32_t* vidx;     // dense variable index of each action's variable, -1 = not solved (value 0)
+  double* remains;
+  double* max_duration;
+  double* latency;
+  double* penalty;         // the variable's current penalty (finish test)
+  const double* share_pen; // CM02: sharing penalty restored once the latency is paid
+  const uint8_t* flags;    // ACT_NO_CNST, ACT_SUSPENDED
+  uint8_t* events;         // EV_* of the last update
+  unsigned long long* umin;  // next-event reduction (bit pattern of a non-negative double)
+  int32_t* nev;            // number of actions with an event in the last update
+  // LAZY update (lmmhip_actions_lazy_*): Action::last_update_ / last_value_ / start_time_ and the
+  // action's ActionHeap entry (date + type) — the heap itself is a min-reduction over `date`.
+  double* last_update;
+  double* last_value;
+  const double* start_time;
+  double* date;            // heap date (+inf when not in the heap)
+  uint8_t* htype;          // HEAP_*
+  int32_t* due;            // compacted due actions (lmmhip_actions_lazy_due)
+  int32_t* ndue;
+  int32_t* err;            // DIE_IMPOSSIBLE of next_occuring_event_lazy (Model.cpp:95-96)
+};
+
+// sizes the host code of more than one translation unit needs
+constexpr int kFbChunk = 1024;             // FairBottleneck: CSC elements per chunk (lmm_fb_kernels.hpp)
+constexpr int kDiagSlot = kMaxBlocks - 4;  // vstat block slots kDiagSlot.. hold the vote diagnostics (kDiag)
+constexpr unsigned kPBlkCap = 1024;        // persistent engine: barriers with per-workgroup timestamps (profiling)
+
 constexpr int kStatRounds = 4096;  // rounds covered by the profiling counters
 constexpr int32_t kUnvoted = -1;   // row target: not evaluated yet
 // A signalling NaN (quiet bit clear, distinctive payload): no fp64 arithmetic returns it, so it can mark "leave this

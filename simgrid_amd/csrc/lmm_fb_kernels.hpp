@@ -1,4 +1,4 @@
-// lmm_fb_kernels.hpp — FairBottleneck::bottleneck_solve on gfx950 (included by lmm_hip.hip).
+// lmm_fb_kernels.hpp — FairBottleneck::bottleneck_solve on gfx950 (included by lmm_hip_fair.hip).
 //
 // One reference round (fair_bottleneck.cpp:59-145) is Jacobi-style: every constraint's share is
 // computed before any variable moves, every variable's increment before any constraint is updated.
@@ -18,8 +18,6 @@
 #include "lmm_dev.hpp"
 
 namespace lmmdev {
-
-constexpr int kFbChunk = 1024;
 
 __global__ void __launch_bounds__(kBlock) fb_init(Dev s) {
   const int64_t n = s.nV > s.nC ? s.nV : s.nC;
@@ -870,21 +868,7 @@ __global__ void __launch_bounds__(kBlock) fbk_update_seq(Dev s, double prec, uin
 //   3  remaining of every listed constraint from xrem, erasure, delisting of the shard's variables
 // Every floating-point operation is the one-context solve's, on the same operands in the same order, so the
 // result is bit-identical to it (and to the reference) whatever the number of shards.
-struct FbOwner {
-  int32_t nc;             // owned constraints
-  int32_t nch;            // their chunks (kFbChunk elements)
-  int64_t mu_off;         // position of this shard's first variable in xmu
-  const int32_t* oc;      // [nc] global id of each owned constraint
-  const uint32_t* optr;   // [nc+1] element offsets
-  const int32_t* ovar;    // [onnz] position of the element's variable in xmu
-  const double* ow;       // [onnz] weight
-  const int32_t* och_o;   // [nch] owned-constraint index of each chunk
-  const uint32_t* och_b;  // [nch] first element of each chunk
-  const int32_t* cpos;    // [nC] position of each constraint's remaining in xrem
-  double* fbd;            // [onnz] increments w * mu (owned CSC order)
-  double* xmu;            // gathered mu (caller's buffer)
-  double* xrem;           // gathered remaining (caller's buffer)
-};
+// (The owned constraints' layout, FbOwner, is in lmm_dev.hpp: the context holds one.)
 
 // phase 1 tail: this shard's mu into its block of the gathered vector (a delisted variable keeps its
 // last mu: its increment still counts, fair_bottleneck.cpp:111-116)

@@ -1,4 +1,4 @@
-// lmm_frontier_kernels.hpp — System::lmm_solve, "frontier" engine (gfx950; included by lmm_hip.hip).
+// lmm_frontier_kernels.hpp — System::lmm_solve, "frontier" engine (gfx950; included by lmm_hip_maxmin.hip).
 //
 // The same local-minimum progressive filling as lmm_maxmin_kernels.hpp (every alive variable
 // votes for the smallest-id constraint of minimal ratio among its constraints; a constraint every alive

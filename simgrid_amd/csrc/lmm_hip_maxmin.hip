@@ -1,0 +1,668 @@
+// lmm_hip_maxmin.hip — the max-min engines of lmmhip_solve (lmm_ctx.hpp): the multi-launch round engine, the
+// frontier engine, the persistent engine with its fallback, and the block-diagonal batch engine.
+#include <cstring>
+
+#include <map>
+#include <mutex>
+#include <thread>
+
+#include "lmm_ctx.hpp"
+#include "lmm_maxmin_kernels.hpp"
+#include "lmm_persist_kernels.hpp"
+#include "lmm_frontier_kernels.hpp"
+#include "lmm_batch_kernels.hpp"
+
+constexpr int64_t kAutoPersistVars = 1 << 18;   // LMMHIP_ENGINE_AUTO: one of the single-GPU small-system engines up to
+constexpr int64_t kAutoPersistMaxVars = 1 << 14;  // this many variables: persistent up to 2^14, frontier above
+
+// Persistent launches are serialised per device, process-wide (solve_maxmin_persist_once): the completion event
+// of each device's last persistent launch, and the number of live contexts on the device (the event is destroyed
+// with the last one, so a device reset between two sets of contexts never leaves a stale event behind).
+namespace {
+std::mutex g_persist_mu;
+// device -> completion event of its last persistent launch (never destroyed at process exit: the runtime may be gone)
+std::map<int, Event>& g_persist_last = *new std::map<int, Event>;
+std::map<int, int> g_persist_users;        // device -> live contexts
+}  // namespace
+
+void persist_ctx_ref(int device, int delta) {
+  std::lock_guard<std::mutex> lk(g_persist_mu);
+  int& n = g_persist_users[device];
+  n += delta;
+  if (n <= 0) {
+    g_persist_users.erase(device);
+    g_persist_last.erase(device);
+  }
+}
+
+// Chunk length under a round-count hint: a chunk that would cross the hinted end E is cut to end at it, and the
+// caller waits for that chunk before queueing more (*stop), so a solve as long as the previous one runs no returning
+// rounds after its last one; a longer one pays one host round trip there, a shorter one is caught by the usual polls.
+// Consecutive solves of a simulation change little, so their round counts do too.  LMMHIP_ROUND_HINT=0: off.
+static int round_hint_chunk(int64_t r, int chunk, int64_t hint, bool* stop) {
+  *stop = false;
+  if (hint > r && r + chunk >= hint) {
+    *stop = true;
+    return int(hint - r);
+  }
+  return chunk;
+}
+
+// The alive-row buffer in use is read by the vote on the device (ctl CTL_BUF); nrows (an upper bound of its
+// rows, refreshed at every poll) only sizes the grid-stride variants' grids.
+static int launch_vote(lmmhip_ctx* c, int64_t r, int64_t nrows) {
+  const Dev& d = c->d;
+  const int G = c->group;
+  const int grid = grid_for(nrows, kBlock);  // one lane per row in the work-queue scan
+  switch (G) {
+  case 4:
+  case 8:  // short rows: one lane per row (more gathers in flight per wave)
+    // the LDS bitmap of changed constraints (one 1024-thread workgroup per CU); below LMMHIP_VOTE_BITS_ROWS alive rows
+    // (host view, A/B knob; 0 = always) the change stamps gathered per row instead: no ~125-KB copy per CU
+    if (int64_t(d.nC) <= int64_t(kBitWords) * 64 && c->vote_bits && nrows >= c->vote_bits_rows) {
+      if (c->profiling && c->vote_diag) {  // measurement: bitmap load alone, filter alone (slot 7)
+        LAUNCH(7, r + 1000000, (mm_vote_lane<kVBlock, true, 2>), c->n_cu, kVBlock, d, int(r));
+        LAUNCH(7, r, (mm_vote_lane<kVBlock, true, 1>), c->n_cu, kVBlock, d, int(r));
+        LAUNCH(7, r, mm_vote_diagcount, grid_for((int64_t(d.nC) + 63) / 64, kBlock), kBlock, d, int(r));
+      }
+      if (d.rdq[0])
+        LAUNCH(2, r, (mm_vote_lane<kVBlock, true, 0, true, true>), c->n_cu, kVBlock, d, int(r));
+      else if (d.crec[0])
+        LAUNCH(2, r, (mm_vote_lane<kVBlock, true, 0, true>), c->n_cu, kVBlock, d, int(r));
+      else
+        LAUNCH(2, r, (mm_vote_lane<kVBlock, true>), c->n_cu, kVBlock, d, int(r));
+    } else if (d.rdq[0]) {
+      LAUNCH(2, r, (mm_vote_lane<kBlock, false, 0, true, true>), grid, kBlock, d, int(r));
+    } else if (d.crec[0]) {
+      LAUNCH(2, r, (mm_vote_lane<kBlock, false, 0, true>), grid, kBlock, d, int(r));
+    } else {
+      LAUNCH(2, r, (mm_vote_lane<kBlock, false>), grid, kBlock, d, int(r));
+    }
+    break;
+  case 16:
+    LAUNCH(2, r, mm_vote<16>, grid, kBlock, d, int(r));
+    break;
+  case 32:
+    LAUNCH(2, r, mm_vote<32>, grid, kBlock, d, int(r));
+    break;
+  default:
+    LAUNCH(2, r, mm_vote<64>, grid, kBlock, d, int(r));
+    break;
+  }
+  return 0;
+}
+
+// Slots: 0 mm_init_cnsts, 1 mm_init_vars, 2 mm_vote, 3 mm_ready, 4 mm_saturate, 5 mm_update,
+// 6 compaction.
+int solve_maxmin(lmmhip_ctx* c, double prec) {
+  Dev& d = c->d;
+  struct RowofOff {  // the other engines never see the row map / row records (their compactions do not
+    Dev& d;          // maintain them)
+    ~RowofOff() {
+      d.crec[0] = d.crec[1] = d.crec[2] = nullptr;
+      d.rdq[0] = d.rdq[1] = nullptr;
+      d.rqst = d.useg = d.ucnt = nullptr;
+    }
+  } rowof_off{d};
+  // packed row records for the re-votes (vote_row: the row's variable and CSR range from one 8-B record and
+  // its successor instead of the cvar / crow arrays, one line per re-vote less): C2 25.94-26.00 vs 26.10-26.17
+  // ms, stress 28.83 vs 29.13 (same box).  LMMHIP_CREC=0: off.
+  d.crec[0] = d.crec[1] = d.crec[2] = nullptr;
+  if ((c->group == 4 || c->group == 8) && env_int("LMMHIP_CREC", 1)) {
+    for (int k = 0; k < 3; k++) {
+      uint2* p = nullptr;
+      if (int rc = scratch(c, c->rounds.crec[k], int64_t(d.nV) + 1, &p))
+        return rc;
+      d.crec[k] = p;
+    }
+  }
+  // ready constraints without the mm_ready pass: the update's workgroups (at most kMaxBlocks, each updating
+  // at most kUSeg constraints) list them for the next round, the vote queues the ones it makes ready (C2
+  // 25.07-25.22 vs 25.34-25.39 ms, stress 28.29 vs 28.46, same box; LMMHIP_RDQ=0: the mm_ready pass)
+  d.rdq[0] = d.rdq[1] = nullptr;
+  d.rqst = d.useg = d.ucnt = nullptr;
+  // (<= kMaxBlocks) Update workgroups: 4 per CU, each with a longer segment, so that the saturation's prefix over
+  // the segment counts is shorter — but enough of them to keep every segment within kUSeg (LMMHIP_UPDQ_BLOCKS).
+  // Round 5, same box: C2 24.52-24.54 ms against 24.84-24.85 with one per 256 constraints (2,048 at C2), stress
+  // 27.86-27.94 vs 28.14; with the saturation cap at 5 per CU below, 24.41-24.45 (stress 27.75-27.77)
+  const int64_t gU_need = (int64_t(d.nC) + kUSeg - 1) / kUSeg;
+  const int64_t gU_rdq = std::max<int64_t>(1, std::min<int64_t>(grid_for(d.nC, kBlock),
+      std::max<int64_t>(gU_need, env_int("LMMHIP_UPDQ_BLOCKS", 4 * c->n_cu))));
+  const int64_t per_blk = int64_t(kBlock) * ((int64_t(d.nC) + gU_rdq * kBlock - 1) / (gU_rdq * kBlock));
+  if (d.crec[0] && env_int("LMMHIP_RDQ", 1) && per_blk <= kUSeg && env_int("LMMHIP_UPD_BLOCKS", c->tune_upd) == 0) {
+    int32_t *q0 = nullptr, *q1 = nullptr, *st = nullptr, *sg = nullptr, *uc = nullptr;
+    const int64_t n = std::max<int64_t>(d.nC, 1);
+    if (int rc = scratch(c, c->rounds.rdq[0], n, &q0) | scratch(c, c->rounds.rdq[1], n, &q1) |
+                 scratch(c, c->rounds.rqst, n, &st) | scratch(c, c->rounds.useg, gU_rdq * kUSeg, &sg) |
+                 scratch(c, c->rounds.ucnt, kMaxBlocks, &uc))
+      return rc;
+    HIPCHK(hipMemsetAsync(st, 0xFF, size_t(n) * sizeof(int32_t), c->stream));
+    HIPCHK(hipMemsetAsync(uc, 0, size_t(kMaxBlocks) * sizeof(int32_t), c->stream));
+    d.rdq[0] = q0;
+    d.rdq[1] = q1;
+    d.rqst = st;
+    d.useg = sg;
+    d.ucnt = uc;
+  }
+  c->vote_bits = env_int("LMMHIP_VOTE_BITS", 1) != 0;
+  c->vote_bits_rows = env_int("LMMHIP_VOTE_BITS_ROWS", 0);
+  const int gC4 = grid_for(d.nC, kBlock / kWave);
+  const int gC = grid_for(d.nC, kBlock);
+  LAUNCH(0, -1, mm_init_cnsts, gC4, kBlock, d, prec);
+  LAUNCH(1, -1, mm_init_vars, grid_for(d.nV, kBlock), kBlock, d);
+  LAUNCH(1, -1, mm_clist, std::min(gC, 2 * c->n_cu), kBlock, d, 1);
+  HIPCHK(hipMemsetAsync(d.chgbits, 0, sizeof(uint64_t) * ((d.nC + 127) / 128 * 2 + 2), c->stream));
+  // Launch-width caps (tuning knobs, environment; 0 = uncapped): fewer blocks cut the fixed per-round
+  // cost of the grid-stride round kernels once the alive set is small.
+  const int cap_upd = env_int("LMMHIP_UPD_BLOCKS", c->tune_upd);
+  // the saturation's grid capped at 4 workgroups per CU (round 5, same box: C2 24.73-24.90 ms against 25.04-25.16
+  // uncapped, i.e. up to kMaxBlocks = 2048; 768: 24.79-25.03, 1280: 24.76-24.81, 1536: 24.83-25.00, 512: 25.42-25.73;
+  // stress 27.99-28.05 vs 28.29-28.36): every workgroup first rebuilds the prefix of the update's segment counts,
+  // and half as many of them still give each ready constraint its waves
+  // (with 4 update workgroups per CU: 5 per CU, 24.41-24.45 ms against 24.52-24.54 at 4 and 24.52-24.60 at 6 / 8)
+  const int cap_sat = env_int("LMMHIP_SAT_BLOCKS", c->tune_sat > 0 ? c->tune_sat : 5 * c->n_cu);
+  auto capped = [](int g, int cap) { return cap > 0 && g > cap ? cap : g; };
+  const int gU = capped(gC, cap_upd);  // mm_update: thread per constraint, identity order
+  const int gUq = int(gU_rdq);          // (ready-queue mode: at most kUSeg constraints per workgroup)
+  // mm_saturate: waves per ready constraint and the grid's block cap (measurement knobs)
+  const int sat_k = env_int("LMMHIP_SAT_WAVES", c->sat_waves);
+  const int sat_max = env_int("LMMHIP_SAT_GRID_MAX", kMaxBlocks);
+  auto sat_grid = [&](int64_t n) { return int(std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, sat_max))); };
+  // Compaction cadence (knobs): alive rows are re-counted every cmp_every rounds and rewritten when
+  // fewer than cmp_pct % of the scanned rows are alive; the alive-constraint list every cl_every rounds.
+  // Both decide and switch buffers on the device (ctl CTL_BUF / CTL_CB): no host round trip.
+  // (round 5, re-swept on the final code, same box: every 48 rounds 24.94-25.08 ms against 25.10-25.21 at 32, 25.49-25.56
+  // at 16, 25.11-25.21 at 64, 25.30-25.34 at 96; stress 28.29-28.37 vs 28.42-28.44)
+  const int cmp_every = env_int("LMMHIP_COMPACT_EVERY", 48);
+  const int cmp_pct = env_int("LMMHIP_COMPACT_PCT", 75);
+  const int cl_every = env_int("LMMHIP_CLIST_EVERY", 8);
+  // Every round fixes at least one variable (progress), so nV + 2 rounds bound it.
+  const int64_t max_rounds = int64_t(d.nV) + 2;
+  // Host view of the sizes (upper bounds: rows and constraints only leave), refreshed at every poll; they
+  // size grids only, the kernels read the exact counts from the control words.
+  int64_t r = 0, last_compact = 0, last_clist = 0, nrows = d.nV, ncl = d.nC;
+  // Termination polls are pipelined (CtlPoll): a chunk queued after the last round is a run of launches that
+  // return at once (CTL_DONE).
+  int chunk = 2;
+  // rounds queued per poll: the host learns of termination one chunk late, so up to 2 x chunk_max no-op
+  // rounds run after the last one (LMMHIP_CHUNK_MAX, A/B knob): C2 25.96-25.99 ms at 16, 26.01 at 8,
+  // 26.15-26.20 at 4; round 5, with compactions every 48 rounds: 25.03-25.06 at 32 against 25.07-25.08 at 16
+  const int64_t hint = env_int("LMMHIP_ROUND_HINT", 1) ? c->hint_rounds_mm : 0;  // (round_hint_chunk)
+  // under a hint no returning rounds follow the last one, and 64-round chunks (fewer polls, a sparser list / compaction
+  // cadence) measured 23.13-23.36 ms against 23.21-23.47 at 32 over five same-box pairs, stress 26.85 vs 26.88
+  // (scripts/gpu_r06_v.sh, _w.sh)
+  const int chunk_max = std::max(2, env_int("LMMHIP_CHUNK_MAX", hint > 0 ? 64 : 32));
+  // Near the end of the solve, short chunks: the rounds queued after the last one are no-op launches of the full
+  // grids (~32 of them after C2's last round with 32-round chunks, rocprofv3 trace of round 5), so once the alive rows
+  // (host view: refreshed at each compaction) fall to LMMHIP_CHUNK_TAIL_PCT % of the variables (default 5), or below
+  // LMMHIP_CHUNK_TAIL_ROWS / the alive-constraint list below LMMHIP_CHUNK_TAIL_CNST (A/B knobs), a chunk is at most
+  // LMMHIP_CHUNK_TAIL rounds (default 4).  Round 5, same box, two passes (scripts/gpu_r05_ctail.sh,
+  // profiles/r05_ab_c2_ctail.json): C2 23.90-23.95 ms at 5e5 rows (5 %) / 4 rounds against 24.10-24.12 without;
+  // 1e6 / 8 and 2e6 / 8 23.92-23.94, 1e6 / 4 23.95-24.07; the constraint-list thresholds (2e4, 1e5) 24.06-24.11.
+  const int64_t ctail_rows = env_int("LMMHIP_CHUNK_TAIL_ROWS",
+                                     int(int64_t(d.nV) * std::max(0, env_int("LMMHIP_CHUNK_TAIL_PCT", 5)) / 100));
+  const int64_t ctail_cnst = env_int("LMMHIP_CHUNK_TAIL_CNST", 0);
+  const int ctail = std::max(1, env_int("LMMHIP_CHUNK_TAIL", 4));
+  auto round_launches = [&](int64_t r) -> int {
+    if (int rc = launch_vote(c, r, nrows))
+      return rc;
+    if (d.rdq[0]) {  // no mm_ready pass: the update's segments (gUq workgroups) and the vote's queue
+      if (sat_k == 1)
+        LAUNCH(4, r, mm_saturate_q<1>, capped(sat_grid(ncl), cap_sat), kBlock, d, int(r), gUq);
+      else if (sat_k == 2)
+        LAUNCH(4, r, mm_saturate_q<2>, capped(sat_grid(2 * ncl), cap_sat), kBlock, d, int(r), gUq);
+      else
+        LAUNCH(4, r, mm_saturate_q<4>, capped(sat_grid(4 * ncl), cap_sat), kBlock, d, int(r), gUq);
+      LAUNCH(5, r, mm_update<true>, gUq, kBlock, d, int(r), prec);
+      return 0;
+    }
+    const int gL = grid_for(ncl, kBlock);
+    LAUNCH(3, r, mm_ready, gL, kBlock, d);
+    if (sat_k == 1)
+      LAUNCH(4, r, mm_saturate<1>, capped(sat_grid(ncl), cap_sat), kBlock, d, int(r), gL);
+    else if (sat_k == 2)
+      LAUNCH(4, r, mm_saturate<2>, capped(sat_grid(2 * ncl), cap_sat), kBlock, d, int(r), gL);
+    else
+      LAUNCH(4, r, mm_saturate<4>, capped(sat_grid(4 * ncl), cap_sat), kBlock, d, int(r), gL);
+    LAUNCH(5, r, mm_update<false>, gU, kBlock, d, int(r), prec);
+    return 0;
+  };
+  // the alive-constraint list and the alive-row compaction at the end of a chunk (their cadence is the chunks')
+  auto chunk_end = [&](int64_t r) -> int {
+    const int gL = grid_for(ncl, kBlock);
+    bool cl = false, cm = false;
+    if (r - last_clist >= cl_every && ncl > 4096) {  // alive-constraint list (order not preserved)
+      LAUNCH(6, r, mm_clist, std::min(gL, 2 * c->n_cu), kBlock, d, 0);
+      last_clist = r;
+      cl = true;
+    }
+    if (r - last_compact >= cmp_every && nrows > 4096) {  // order-preserving compaction of the alive rows
+      const int nblk = int((nrows + kCompactRows - 1) / kCompactRows);
+      LAUNCH(6, r, cmp_count, nblk, kBlock, d);
+      LAUNCH(6, r, cmp_scan, 1, 1024, d, nblk, cmp_pct);
+      LAUNCH(6, r, cmp_write, nblk, kBlock, d);
+      last_compact = r;
+      cm = true;
+    }
+    if (cl || cm)
+      LAUNCH(6, r, mm_flip, 1, 1, d, int(cl), int(cm));
+    return 0;
+  };
+  CtlPoll poll;
+  if (int rc = poll.init(c))
+    return rc;
+  for (;;) {
+    bool stop = false;
+    const int n = round_hint_chunk(r, chunk, hint, &stop);
+    for (int k = 0; k < n; k++, r++)
+      if (int rc = round_launches(r))
+        return rc;
+    LAUNCH(6, r, mm_done, 1, kBlock, d, d.rdq[0] ? gUq : gU);
+    if (int rc = chunk_end(r))
+      return rc;
+    const int32_t* h = nullptr;
+    if (int rc = poll.step(d, r, stop, &h))
+      return rc;
+    if (h) {
+      if (h[CTL_DONE])
+        break;
+      ncl = h[CTL_NCL0 + h[CTL_CB]];
+      nrows = h[CTL_NROWS + h[CTL_BUF]];
+    }
+    if (r > max_rounds)
+      return fail(LMMHIP_E_NOCONVERGE, "maxmin round guard tripped");
+    if (chunk < chunk_max)
+      chunk = std::min(2 * chunk, chunk_max);
+    // (the short tail chunks stay under a hint too: dropping them measured 23.10 against 23.05-23.08 ms,
+    // scripts/gpu_r06_t.sh)
+    if ((nrows <= ctail_rows || ncl <= ctail_cnst) && chunk > ctail)
+      chunk = ctail;
+  }
+  if (int rc = poll_ctl(c))  // (the queued tail has run: final words for the stats)
+    return rc;
+  c->hint_rounds_mm = int64_t(c->h_ctl.p[CTL_LASTR]) + 1;
+  return 0;
+}
+
+// Frontier engine (lmm_frontier_kernels.hpp): three launches per round, work proportional to the touched
+// constraints and the moving votes.  Slots: 2 fr_vote, 4 fr_sat (+ fr_sat_big), 5 fr_update, 6 the per-chunk
+// control-word copy; 0 / 1 init.
+int solve_maxmin_frontier(lmmhip_ctx* c, double prec) {
+  Dev d = c->d;  // (a copy: the frontier's buffers stay out of the context's Dev, which the other engines use)
+  if (!c->vote_diag)  // per-round diagnostic counters only on request (LMMHIP_VOTE_DIAG): they cost atomics
+    d.vstat = nullptr;
+  const int64_t nnz = std::max<int64_t>(d.nnz, 1);
+  const int nblk = int((int64_t(d.nC) + kFB - 1) / kFB);  // fr_update / fr_vote (/ fr_sat<256>) workgroups
+  const int nblkS = int(std::max<int64_t>(1, (int64_t(d.nC) + kFS - 1) / kFS));  // fr_sat workgroups
+  int2* cs = nullptr;
+  int32_t* md = nullptr;
+  int rc = scratch(c, c->frontier.c2s, nnz, &cs);
+  rc = rc ? rc : scratch(c, c->frontier.pvb, std::max<int64_t>(d.nV, 1), &d.pvb);
+  rc = rc ? rc : scratch(c, c->frontier.slot, nnz, &d.vslot);
+  rc = rc ? rc : scratch(c, c->frontier.minfl, std::max<int64_t>(d.nC, 1), &d.minfl);
+  rc = rc ? rc : scratch(c, c->frontier.key, std::max<int64_t>(d.nC, 1), &d.key32);
+  rc = rc ? rc : scratch(c, c->frontier.qa, nnz, &d.fq_a);
+  rc = rc ? rc : scratch(c, c->frontier.qb, nnz, &d.fq_b);
+  rc = rc ? rc : scratch(c, c->frontier.qn, int64_t(nblk) + 1, &d.fq_n);
+  rc = rc ? rc : scratch(c, c->frontier.md, 1, &md);
+  if (rc)
+    return rc;
+  d.csr_cs = cs;
+  if (!c->frontier.map_ok) {  // once per uploaded structure
+    HIPCHK(hipMemsetAsync(md, 0, sizeof(int32_t), c->stream));
+    if (d.nnz > 0) {
+      hipLaunchKernelGGL(fr_c2s, dim3(grid_for(d.nC, kBlock / kWave)), dim3(kBlock), 0, c->stream, d, cs, md);
+      HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(&c->frontier.maxdeg, md, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->frontier.map_ok = true;
+  }
+  // constraints of more CSC chunks than this saturate in fr_sat_big, kFrBigWaves waves each over the whole grid
+  // (LMMHIP_FR_BIGCH, A/B knob: fat-tree core links' chunk chains in C4)
+  const int bigch = std::max(1, env_int("LMMHIP_FR_BIGCH", kFrBigCh));
+  const bool big = c->frontier.maxdeg > bigch * kWave;
+  const int bigw = std::max(1, env_int("LMMHIP_FR_BIGW", kFrBigWaves));  // waves per big constraint (A/B knob)
+  // (round 6, removed after their A/Bs: the re-vote reading the floors with the keys, LMMHIP_FR_MFEARLY, and the round
+  // engine's chunk body in fr_sat, LMMHIP_FR_SATOLD — both slower on C2 and C4, scripts/gpu_fr_ab.sh)
+  // re-votes keep 16 row elements in registers when the mean row is longer than 8 (LMMHIP_FR_R16=0: 8)
+  const bool long_rows = c->group > 8 && env_int("LMMHIP_FR_R16", 1) != 0;
+  // fr_vote: segments per workgroup, so that the grid still covers the chip twice (C2: 4, small systems: 1)
+  const int spb = int(std::max<int64_t>(1, std::min<int64_t>(kFVS, int64_t(nblk) / (2 * int64_t(c->n_cu)))));
+  // fr_sat workgroup: kFS threads (the round-4 choice on C2-size systems) unless that leaves the chip mostly
+  // idle — C4 (25 workgroups of kFS): 3.37-3.40 ms with 256-thread workgroups against 3.49
+  const int sat_b0 = int64_t(nblkS) >= 2 * int64_t(c->n_cu) ? kFS : 256;
+  const int sat_b = env_int("LMMHIP_FR_SATB", sat_b0) == 256 ? 256 : kFS;
+  // fr_update: every constraint's state loaded with its key (one dependent level less) on the small systems, where the
+  // 256-thread saturation workgroups run (LMMHIP_FR_UPDSPEC, A/B knob)
+  const int upd_spec = env_int("LMMHIP_FR_UPDSPEC", sat_b == 256 ? 1 : 0);
+  const int gC4 = grid_for(d.nC, kBlock / kWave);
+  LAUNCH(0, -1, mm_init_cnsts, gC4, kBlock, d, prec);
+  LAUNCH(1, -1, fr_init_vars, grid_for(std::max<int64_t>(std::max<int64_t>(d.nV, d.nC), d.nnz / 4), kBlock), kBlock, d);
+  const int64_t max_rounds = int64_t(d.nV) + 2;  // every round fixes a variable (progress)
+  const int gbig = std::min(kMaxBlocks, 4 * c->n_cu);
+  auto round_launches = [&](int64_t r) -> int {
+    if (r == 0) {
+      LAUNCH(2, r, fr_vote_all, grid_for(d.nV, kBlock), kBlock, d);
+      LAUNCH(2, r, fr_minfl_all, grid_for(d.nC, kBlock / 16), kBlock, d);
+    } else if (long_rows) {  // (LV08 routes: ~12 elements per row)
+      LAUNCH(2, r, fr_vote<16>, (nblk + spb - 1) / spb, kFB, d, int(r), spb);
+    } else {
+      LAUNCH(2, r, fr_vote<8>, (nblk + spb - 1) / spb, kFB, d, int(r), spb);
+    }
+    if (sat_b == 256)
+      LAUNCH(4, r, fr_sat<256>, nblk, 256, d, int(r), bigch);
+    else
+      LAUNCH(4, r, fr_sat<kFS>, nblkS, kFS, d, int(r), bigch);
+    if (big)
+      LAUNCH(4, r, fr_sat_big, gbig, kBlock, d, int(r), bigw);
+    LAUNCH(5, r, fr_update, nblk, kFB, d, int(r), prec, upd_spec);
+    return 0;
+  };
+  int64_t r = 0;
+  // pipelined termination polls, as solve_maxmin (CtlPoll); rounds queued after the last one return at once.  (Round 6,
+  // measured and not kept: fr_vote storing "done" into a pinned host word itself, so that a poll is the event
+  // alone without mm_ctl_out — C4 3.083-3.091 ms against 3.060-3.069, scripts/gpu_r06_p.sh; and the launches paced
+  // by a per-round progress word, 2-5 rounds queued ahead — 3.17-3.28 against 3.12, scripts/gpu_r06_o.sh.)
+  int chunk = 2;
+  // rounds queued per poll: the host learns of termination one chunk late, so up to 2 x chunk_max no-op
+  // rounds run after the last one (LMMHIP_CHUNK_MAX, A/B knob): C4 3.48 ms at 8, 3.51-3.53 at 4, 3.55 at 16
+  // (short rounds: the no-op tail is a larger share)
+  const int chunk_max = std::max(2, env_int("LMMHIP_CHUNK_MAX", 8));
+  CtlPoll poll;
+  if (int rc = poll.init(c))
+    return rc;
+  const int64_t hint = env_int("LMMHIP_ROUND_HINT", 1) ? c->hint_rounds_fr : 0;
+  // with a hint the returning rounds after the last one are gone, and what longer chunks cost is with them: fewer
+  // polls (mm_ctl_out, 3.6 us of kernel each) up to the hinted end (LMMHIP_HINT_CHUNK_MAX, A/B knob)
+  const int chunk_cap = hint > 0 ? std::max(chunk_max, env_int("LMMHIP_HINT_CHUNK_MAX", 32)) : chunk_max;
+  // and the first chunk need not be short either (its point is an early poll for systems of few rounds)
+  if (hint > 0)
+    chunk = std::max(chunk, std::min(chunk_cap, env_int("LMMHIP_HINT_CHUNK0", chunk_cap)));
+  for (;;) {
+    bool stop = false;
+    const int n = round_hint_chunk(r, chunk, hint, &stop);
+    for (int k = 0; k < n; k++, r++)
+      if (int rc = round_launches(r))
+        return rc;
+    const int32_t* h = nullptr;
+    if (int rc = poll.step(d, r, stop, &h))
+      return rc;
+    if (h && h[CTL_DONE])
+      break;
+    if (r > max_rounds)
+      return fail(LMMHIP_E_NOCONVERGE, "maxmin round guard tripped");
+    if (chunk < chunk_cap)
+      chunk = std::min(2 * chunk, chunk_cap);
+  }
+  if (int rc = poll_ctl(c))
+    return rc;
+  c->hint_rounds_fr = int64_t(c->h_ctl.p[CTL_ROUNDS]) + 1;
+  return 0;
+}
+
+int engine_of(const lmmhip_ctx* c) {
+  // LMMHIP_ENGINE=rounds|persistent|frontier overrides the context's engine; "auto" (or any other value,
+  // which is ignored) leaves the context's choice in place
+  const char* e = std::getenv("LMMHIP_ENGINE");
+  int eng = c->engine;
+  if (e && std::strcmp(e, "rounds") == 0)
+    eng = LMMHIP_ENGINE_ROUNDS;
+  if (e && std::strcmp(e, "persistent") == 0)
+    eng = LMMHIP_ENGINE_PERSISTENT;
+  if (e && std::strcmp(e, "frontier") == 0)
+    eng = LMMHIP_ENGINE_FRONTIER;
+  // the profiling mode times every phase launch: a multi-launch engine
+  if (c->profiling)
+    return eng == LMMHIP_ENGINE_FRONTIER ? LMMHIP_ENGINE_FRONTIER : LMMHIP_ENGINE_ROUNDS;
+  if (eng != LMMHIP_ENGINE_AUTO)
+    return eng;
+  // AUTO (measured): one launch per solve where the host round-trips and launches of the
+  // round chain dominate (small systems: a tie at C4, 1e5 variables, and ahead below); the round chain
+  // above, where the kernel boundaries (~1.5 us) are cheaper than grid barriers (~4 us) and per-launch
+  // grids keep 32 waves per CU in flight instead of 16
+  // round 4: the frontier engine between the two (C4, 1e5 LV08 flows: 3.54 ms against 4.34 persistent and
+  // 4.48 rounds), the round engine above (C2: 25.8 against 28.2 frontier)
+  if (int64_t(c->d.nV) <= kAutoPersistMaxVars)
+    return LMMHIP_ENGINE_PERSISTENT;
+  return int64_t(c->d.nV) <= kAutoPersistVars ? LMMHIP_ENGINE_FRONTIER : LMMHIP_ENGINE_ROUNDS;
+}
+
+// One persistent launch per solve (lmm_persist_kernels.hpp): one 1024-thread workgroup per CU, all
+// resident (the occupancy query admits exactly one per CU); every barrier wait is bounded, so a fault in
+// the protocol ends the launch with CTL_ERR instead of hanging the GPU.
+// Persistent launches are serialised per device, process-wide: a persistent grid needs every CU for one
+// workgroup at once (its barriers rely on co-residency), so two of them running side by side — two Systems
+// on two streams, or two threads — could each hold part of the chip and wait on the other.  Each persistent
+// launch waits (on its own stream, no host blocking) for the previous one's completion event
+// (g_persist_last, above).
+
+static int solve_maxmin_persist_once(lmmhip_ctx* c, double prec, bool* closed) {
+  Dev d = c->d;
+  d.vstat = nullptr;
+  const bool bits = int64_t(d.nC) <= int64_t(kPBitWords) * 64;
+  // 8 row elements in registers in the re-vote, longer rows loop over the rest.  (A 10-register variant for
+  // long mean rows — C4's LV08 routes, 11.7 elements, when C4 still ran here — sat at the 128-VGPR budget of a
+  // 1024-thread workgroup and spilled once the launch rendezvous moved ahead of the init; C4 runs on the
+  // frontier engine since round 4, and AUTO keeps this engine for systems of at most 2^14 variables.)
+  const void* kern = bits ? reinterpret_cast<const void*>(&mm_persist<true, 8>)
+                          : reinterpret_cast<const void*>(&mm_persist<false, 8>);
+  if (!c->pbar.p)
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->pbar.p), BAR_WORDS * sizeof(unsigned)));
+  int per_cu = 0;
+  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kPB, 0));
+  if (per_cu < 1)
+    return fail(LMMHIP_E_HIP, "persistent maxmin kernel: not one workgroup per CU (occupancy query)");
+  const int grid = c->n_cu;
+  c->persist_grid = grid;
+  const int max_rounds = int(std::min<int64_t>(int64_t(d.nV) + 2, INT32_MAX - 1));
+  const int cmp_every = env_int("LMMHIP_COMPACT_EVERY", 16);
+  unsigned* barw = c->pbar.p;
+  long long* pt = nullptr;
+  unsigned pt_cap = 0;
+  if (c->persist_prof) {  // barrier timestamps (lmmhip_persist_profile)
+    pt_cap = kPersistProfCap;
+    const size_t bytes = sizeof(long long) * (2 * size_t(pt_cap) + 2 * size_t(kPBlkCap) * size_t(grid));
+    if (!c->ptime.p)
+      HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->ptime.p), bytes));
+    HIPCHK(hipMemsetAsync(c->ptime.p, 0, bytes, c->stream));
+    pt = c->ptime.p;
+  }
+  int sysf = env_int("LMMHIP_PERSIST_SYSFENCE", 0);
+  // launch rendezvous deadline (bar_rdv): the grid's workgroups are dispatched within microseconds when the CUs
+  // are free, so 20 ms of waiting means part of the chip is held by someone else
+  long long rdv_ticks = 100000LL * env_int("LMMHIP_PERSIST_RDV_MS", 20);  // 100 MHz wall clock
+  int32_t* hflag = c->d_rdv;
+  void* args[] = {&d, &barw, &prec, const_cast<int*>(&max_rounds), const_cast<int*>(&cmp_every), &pt, &pt_cap, &sysf,
+                  &rdv_ticks, &hflag};
+  // A plain launch on the context's stream: the occupancy query above guarantees one workgroup per CU, so the
+  // n_cu workgroups are co-resident once the stream's earlier work has drained and nothing else holds CUs; the
+  // rendezvous deadline and the bounded barrier waits cover the case where something does.
+  // (Not hipLaunchCooperativeKernel: it runs the same kernel through the runtime's device-wide cooperative queue,
+  // whose teardown at process exit crashed inside the HSA runtime under rocprofv3 — SIGSEGV in libamdhip64's exit
+  // handler)
+  {
+    std::lock_guard<std::mutex> lk(g_persist_mu);
+    Event& last = g_persist_last[c->device];
+    if (last.p && hipStreamWaitEvent(c->stream, last.p, 0) != hipSuccess) {  // (a stale event: make a new one)
+      (void)hipGetLastError();
+      (void)last.reset();
+    }
+    if (!last.p)
+      HIPCHK(hipEventCreateWithFlags(&last.p, hipEventDisableTiming));
+    // the barrier words are reset behind the previous persistent launch (whose late workgroups, after a closed
+    // rendezvous, still read them)
+    HIPCHK(hipMemsetAsync(c->pbar.p, 0, BAR_WORDS * sizeof(unsigned), c->stream));
+    HIPCHK(hipMemsetAsync(d.chgbits, 0, sizeof(uint64_t) * ((d.nC + 127) / 128 * 2 + 2), c->stream));
+    __atomic_store_n(c->h_rdv.p, 0, __ATOMIC_RELEASE);
+    HIPCHK(hipLaunchKernel(kern, dim3(grid), dim3(kPB), args, 0, c->stream));
+    HIPCHK(hipEventRecord(last.p, c->stream));
+  }
+  c->stats.kernel_launches[2] += 1;
+  HIPCHK(hipEventRecord(c->ev1.p, c->stream));
+  c->ev1_done = true;
+  // wait for the launch, or for its rendezvous to close (the mapped word), whichever comes first
+  for (;;) {
+    const hipError_t q = hipEventQuery(c->ev1.p);
+    if (q == hipSuccess)
+      break;
+    if (q != hipErrorNotReady)
+      HIPCHK(q);
+    if (__atomic_load_n(c->h_rdv.p, __ATOMIC_ACQUIRE)) {  // closed: no workgroup of it has written anything
+      // The launch is left behind with its late workgroups (they return at once when they get CUs).  A context
+      // on its own stream moves to a new one, so the fallback and everything after it run on the free CUs now;
+      // a caller-provided stream keeps its order (the fallback then waits for the late workgroups).
+      *closed = true;
+      if (c->stream == c->own_stream.p) {
+        Stream ns;
+        HIPCHK(hipStreamCreateWithFlags(&ns.p, hipStreamNonBlocking));
+        std::swap(ns.p, c->own_stream.p);
+        c->stream = c->own_stream.p;
+        c->retired_streams.push_back(std::move(ns));
+      }
+      return fail(LMMHIP_E_HIP, "persistent maxmin kernel: the launch rendezvous closed (grid not co-resident)");
+    }
+    std::this_thread::yield();
+  }
+  if (int rc = poll_ctl(c))
+    return rc;
+  if (c->h_ctl.p[CTL_ERR] == 1)
+    return fail(LMMHIP_E_HIP, "persistent maxmin kernel: a grid-barrier wait timed out");
+  if (c->h_ctl.p[CTL_ERR] == 2)
+    return fail(LMMHIP_E_NOCONVERGE, "maxmin round guard tripped");
+  return 0;
+}
+
+// A persistent solve that cannot run — its launch rendezvous closed because part of the grid could not become
+// resident within LMMHIP_PERSIST_RDV_MS (another kernel or process holding CUs: bar_rdv), or, later, a
+// grid-barrier wait timed out (CTL_ERR 1) — is not an error of the system: the solve is re-run by the
+// multi-launch engine, whose results are bit-identical (tests/test_gpu_engines.py).  The next
+// LMMHIP_PERSIST_COOLDOWN solves of the context then take the multi-launch engine directly (a
+// fallback that did not stick made every later solve under sustained contention pay the wait again).
+
+// Streams left behind by closed persistent launches (their late workgroups may still run): each one whose work has
+// drained is destroyed; past kRetiredCap of them the oldest is waited for (under sustained contention
+// the list grew by one stream per close without bound).
+constexpr size_t kRetiredCap = 8;
+static int reap_retired_streams(lmmhip_ctx* c) {
+  auto& v = c->retired_streams;
+  for (size_t i = 0; i < v.size();) {
+    const hipError_t q = hipStreamQuery(v[i].p);
+    if (q == hipErrorNotReady) {
+      i++;
+      continue;
+    }
+    v.erase(v.begin() + long(i));  // (destroys it)
+  }
+  while (v.size() > kRetiredCap) {
+    HIPCHK(hipStreamSynchronize(v.front().p));
+    v.erase(v.begin());
+  }
+  return 0;
+}
+
+int solve_maxmin_persist(lmmhip_ctx* c, double prec) {
+  if (int rc = reap_retired_streams(c))
+    return rc;
+  if (c->persist_cool > 0) {
+    c->persist_cool -= 1;
+    return solve_maxmin(c, prec);
+  }
+  c->h_ctl.p[CTL_ERR] = 0;
+  bool closed = false;
+  const int rc = solve_maxmin_persist_once(c, prec, &closed);
+  if (!closed && (rc != LMMHIP_E_HIP || c->h_ctl.p[CTL_ERR] != 1))
+    return rc;
+  c->persist_fallbacks += 1;
+  c->persist_cool = env_int("LMMHIP_PERSIST_COOLDOWN", 64);
+  HIPCHK(hipMemsetAsync(c->d.ctl, 0, CTL_ALLOC * sizeof(int32_t), c->stream));
+  c->ev1_done = false;
+  return solve_maxmin(c, prec);
+}
+
+// ---- block-diagonal batches: one workgroup per system, the system in LDS (lmm_batch_kernels.hpp) ----
+constexpr size_t kBatchLdsMax = 64 * 1024;  // per workgroup; larger systems take the global engines
+
+bool batch_fits(const lmmhip_ctx* c) {
+  if (c->bt_n <= 0 || c->profiling)
+    return false;
+  if (const char* e = std::getenv("LMMHIP_BATCH"); e && *e == '0')
+    return false;
+  return c->bt_max_nv < 65535 && c->bt_max_nc < 65535 && c->bt_max_nnz < 65535 &&
+         batch_lds_bytes(c->bt_max_nv, c->bt_max_nc, c->bt_max_nnz) <= kBatchLdsMax;
+}
+
+int solve_maxmin_batch(lmmhip_ctx* c, double prec) {
+  const size_t lds = batch_lds_bytes(c->bt_max_nv, c->bt_max_nc, c->bt_max_nnz);
+  int per_cu = 0;
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mm_batch_lds),
+                             hipFuncAttributeMaxDynamicSharedMemorySize, int(kBatchLdsMax)));
+  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&mm_batch_lds), kBB,
+                                                      lds));
+  const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(c->bt_n, int64_t(c->n_cu) * std::max(per_cu, 1)));
+  if (grid > c->bt_cap) {
+    HIPCHK(c->bt_rounds.reset());
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->bt_rounds.p), sizeof(int32_t) * size_t(grid)));
+    c->bt_cap = grid;
+  }
+  Dev d = c->d;
+  hipLaunchKernelGGL(mm_batch_lds, dim3(unsigned(grid)), dim3(kBB), lds, c->stream, d, c->bt_voff.p, c->bt_coff.p,
+                     c->bt_n, prec, c->bt_max_nv, c->bt_max_nc, c->bt_max_nnz, c->bt_rounds.p);
+  HIPCHK(hipGetLastError());
+  c->stats.kernel_launches[2] += 1;
+  HIPCHK(hipEventRecord(c->ev1.p, c->stream));
+  c->ev1_done = true;
+  hipLaunchKernelGGL(mm_batch_rounds, dim3(1), dim3(kBlock), 0, c->stream, c->bt_rounds.p, int(grid), d.ctl);
+  HIPCHK(hipGetLastError());
+  if (int rc = poll_ctl(c))
+    return rc;
+  if (c->h_ctl.p[CTL_ERR] == 2)
+    return fail(LMMHIP_E_NOCONVERGE, "batch maxmin round guard tripped");
+  return 0;
+}
+
+int lmmhip_set_batch(lmmhip_ctx* c, int64_t nsys, const int64_t* var_off, const int64_t* cnst_off) {
+  if (!c || !c->uploaded)
+    return fail(LMMHIP_E_STATE, "no system uploaded");
+  c->bt_n = 0;
+  if (nsys == 0)
+    return 0;
+  if (nsys < 0 || !var_off || !cnst_off)
+    return fail(LMMHIP_E_ARG, "bad batch arguments");
+  const Dev& d = c->d;
+  if (var_off[0] != 0 || var_off[nsys] != d.nV || cnst_off[0] != 0 || cnst_off[nsys] != d.nC)
+    return fail(LMMHIP_E_ARG, "batch offsets must cover the uploaded system");
+  for (int64_t i = 0; i < nsys; i++)
+    if (var_off[i + 1] < var_off[i] || cnst_off[i + 1] < cnst_off[i])
+      return fail(LMMHIP_E_ARG, "batch offsets not monotone");
+  HIPCHK(hipSetDevice(c->device));
+  std::vector<uint32_t> vp(size_t(d.nV) + 1);
+  HIPCHK(hipMemcpyAsync(vp.data(), d.var_ptr, vp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  int64_t mv = 0, mc = 0, me = 0;
+  for (int64_t i = 0; i < nsys; i++) {
+    mv = std::max(mv, var_off[i + 1] - var_off[i]);
+    mc = std::max(mc, cnst_off[i + 1] - cnst_off[i]);
+    me = std::max(me, int64_t(vp[size_t(var_off[i + 1])]) - int64_t(vp[size_t(var_off[i])]));
+  }
+  HIPCHK(c->bt_voff.reset());
+  HIPCHK(c->bt_coff.reset());
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->bt_voff.p), sizeof(int64_t) * size_t(nsys + 1)));
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->bt_coff.p), sizeof(int64_t) * size_t(nsys + 1)));
+  HIPCHK(hipMemcpyAsync(c->bt_voff.p, var_off, sizeof(int64_t) * size_t(nsys + 1), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->bt_coff.p, cnst_off, sizeof(int64_t) * size_t(nsys + 1), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemsetAsync(d.ctl + CTL_ERR, 0, sizeof(int32_t), c->stream));
+  hipLaunchKernelGGL(mm_batch_check, dim3(unsigned(std::min<int64_t>(nsys, 4096))), dim3(kBlock), 0, c->stream, d,
+                     c->bt_voff.p, c->bt_coff.p, nsys, d.ctl + CTL_ERR);
+  HIPCHK(hipGetLastError());
+  int32_t bad = 0;
+  HIPCHK(hipMemcpyAsync(&bad, d.ctl + CTL_ERR, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (bad)
+    return fail(LMMHIP_E_ARG, "batch: an element links two declared systems (not block-diagonal)");
+  c->bt_n = nsys;
+  c->bt_max_nv = int(mv);
+  c->bt_max_nc = int(mc);
+  c->bt_max_nnz = int(me);
+  return 0;
+}

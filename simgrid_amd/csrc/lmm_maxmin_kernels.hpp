@@ -1,4 +1,4 @@
-// lmm_maxmin_kernels.hpp — System::lmm_solve on gfx950 (included by lmm_hip.hip).
+// lmm_maxmin_kernels.hpp — System::lmm_solve on gfx950 (included by lmm_hip_maxmin.hip).
 //
 // Local-minimum parallel progressive filling with persistent votes:
 //   every alive variable votes for ONE constraint of minimal ratio among its constraints (ties:
@@ -25,50 +25,8 @@
 
 namespace lmmdev {
 
-// Per-element usage w / penalty of every CSC element (maxmin.cpp:531-533's summand), computed at upload
-// and whenever the penalties change, so the per-solve init streams it instead of gathering pen[v].
-// Per CSC element: usage w / penalty and the penalty (with every penalty change), and — rows = 1, with every
-// structure change — its variable's CSR row.
-__global__ void __launch_bounds__(kBlock) mm_elem_usage(Dev s, int rows) {
-  for (int64_t j = int64_t(blockIdx.x) * kBlock + threadIdx.x; j < s.nnz; j += int64_t(gridDim.x) * kBlock) {
-    const int32_t v = s.csc_v[j];
-    const double p = s.pen[v];
-    s.csc_u[j] = s.csc_w[j] / p;
-    s.csc_p[j] = p;
-    if (rows)
-      s.csc_row[j] = (unsigned long long)s.var_ptr[v] | ((unsigned long long)s.var_ptr[v + 1] << 32);
-  }
-}
-
-// cdup (zeroed before): constraints holding two elements of one variable; every constraint of a row longer
-// than 64 elements is flagged without the pairwise test.
-__global__ void __launch_bounds__(kBlock) mm_dup_check(Dev s) {
-  for (int64_t v = int64_t(blockIdx.x) * kBlock + threadIdx.x; v < s.nV; v += int64_t(gridDim.x) * kBlock) {
-    const uint32_t b = s.var_ptr[v], e = s.var_ptr[v + 1];
-    if (e - b > 64) {
-      for (uint32_t i = b; i < e; i++)
-        s.cdup[s.csr_c[i]] = 1;
-      continue;
-    }
-    if (e - b <= 16) {  // the row in registers, its loads in flight together
-      int32_t cc[16];
-#pragma unroll
-      for (int i = 0; i < 16; i++)
-        cc[i] = b + i < e ? s.csr_c[b + i] : -1 - i;
-#pragma unroll
-      for (int i = 0; i < 16; i++)
-#pragma unroll
-        for (int j = i + 1; j < 16; j++)
-          if (cc[i] >= 0 && cc[i] == cc[j])
-            s.cdup[cc[i]] = 1;
-      continue;
-    }
-    for (uint32_t i = b; i < e; i++)
-      for (uint32_t j = i + 1; j < e; j++)
-        if (s.csr_c[i] == s.csr_c[j])
-          s.cdup[s.csr_c[i]] = 1;
-  }
-}
+// (mm_elem_usage, mm_dup_check, mm_ctl_out, mm_saturated and rs_touched, which other parts of the driver launch too,
+// are in lmm_common_kernels.hpp.)
 
 // Init, one wave per constraint: maxmin.cpp:520-555.  remaining = bound; skipped when
 // bound <= bound*prec; usage = sum (SHARED) or max (FATPIPE) of w/p over the active elements.
@@ -453,16 +411,6 @@ __global__ void __launch_bounds__(kBlock) mm_clist(Dev s, int from_all) {
   }
 }
 
-// The control words into a pinned host slot, written by the GPU itself (mapped memory, system-scope release):
-// a copy-engine transfer on the stream cost a 20-40 us gap before the next kernel at every poll (~1 ms per C2
-// solve in the rocprofv3 trace).
-__global__ void mm_ctl_out(Dev s, int32_t* dst) {
-  const int i = threadIdx.x;
-  if (i < CTL_WORDS)
-    __hip_atomic_store(dst + i, s.ctl[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-}
-
 // After a list re-compaction and / or a row compaction: switch the buffers in use (one thread).
 __global__ void mm_flip(Dev s, int clist, int rows) {
   if (s.ctl[CTL_DONE])
@@ -696,7 +644,6 @@ __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64
 // kDiag (measurement only, LMMHIP_VOTE_DIAG): 1 = the filter alone (rows queued, none resolved), with
 // per-round counters of target-changed / sensitive / queued rows in vstat's kDiagSlot.
 constexpr int kQW = 2 * kWave;  // per-wave queue capacity
-constexpr int kDiagSlot = kMaxBlocks - 4;  // vstat block slots kDiagSlot.. hold the vote diagnostics (kDiag)
 
 // The wave's row range [wlo, whi) of the workgroup's rows [lo, hi).
 __device__ __forceinline__ void vote_wave_range(int64_t lo, int64_t hi, int64_t& wlo, int64_t& whi) {
@@ -1825,42 +1772,6 @@ template <bool kRdq = false> __global__ void __launch_bounds__(kBlock) mm_update
     arec[8] = wc[1];
   }
 #endif
-}
-
-// Saturated set of the solved system: sat(c) = NOT double_positive(bound - U_c,
-// bound * prec) with U_c = Constraint::get_usage() (maxmin.cpp:948-961: sum, or max for FATPIPE, of
-// w * x over the enabled elements of weight > 0 — exactly the flattened CSC of c).  One wave per
-// constraint.  FairBottleneck: sat(c) = c was erased (fair_bottleneck.cpp:129-140, ratio = +inf).
-__global__ void __launch_bounds__(kBlock) mm_saturated(Dev s, double prec, int fair, uint8_t* out) {
-  const int lane = threadIdx.x & (kWave - 1);
-  for (int64_t c = (int64_t(blockIdx.x) * kBlock + threadIdx.x) / kWave; c < s.nC;
-       c += int64_t(gridDim.x) * (kBlock / kWave)) {
-    if (fair) {
-      if (lane == 0)
-        out[c] = s.ratio[c] != 0.0;
-      continue;
-    }
-    const bool fat = s.cflags[c] & 1;
-    double u = 0.0;
-    for (uint32_t j = s.cnst_ptr[c] + lane; j < s.cnst_ptr[c + 1]; j += kWave) {
-      const double t = s.csc_w[j] * s.x[s.csc_v[j]];
-      u = fat ? fmax(u, t) : u + t;
-    }
-    u = fat ? wave_max(u) : wave_sum(u);
-    if (lane == 0) {
-      const double b = s.cbound[c];
-      out[c] = !((b - u) > b * prec);
-    }
-  }
-}
-
-// Variables of the solved system in the caller's id space: dense index d -> host slot (resident
-// flatten: dv = exclusive scan of the membership mask vm), written at out[d] (ascending slots).
-__global__ void __launch_bounds__(kBlock) rs_touched(int64_t nslots, const int64_t* vm, const int64_t* dv,
-                                                     int32_t* out) {
-  for (int64_t v = int64_t(blockIdx.x) * kBlock + threadIdx.x; v < nslots; v += int64_t(gridDim.x) * kBlock)
-    if (vm[v])
-      out[dv[v]] = int32_t(v);
 }
 
 // Termination (maxmin.cpp:680): no constraint left in the light table after the last update.

@@ -28,7 +28,6 @@ constexpr int kPW = kPB / kWave;     // waves per workgroup
 constexpr int kPBitWords = 16384;    // LDS bitmap: 2^20 constraints (128 KB)
 constexpr int kPFilt = 4;            // rows per thread per filter step
 constexpr long long kSpinTicks = 400000000;  // 4 s of the 100 MHz wall clock: a barrier wait gives up
-constexpr unsigned kPBlkCap = 1024;          // barriers with per-workgroup timestamps (profiling)
 
 // Grid-barrier words (zeroed by the host before every launch), each counter on its own 64-B line.
 enum : int {

@@ -26,19 +26,7 @@
 
 namespace lmmdev {
 
-// Resident mirror (host ids; capacities grow on demand, contents survive growth).
-struct ResDev {
-  int32_t* e_cnst;   // [capE] constraint of element slot e
-  double* e_w;       // [capE] consumption weight
-  uint8_t* e_fl;     // [capE] bit0: in its constraint's enabled list
-  int64_t* v_ebase;  // [capV] first element slot of the variable's slab
-  int32_t* v_n;      // [capV] elements in use; -1 = dead variable (lmm_system.cpp; loops `i < n` skip it, rs_apply_v validates it)
-  double* v_pen;     // [capV] sharing penalty
-  double* v_bound;   // [capV] bound (-1 = none)
-  double* c_bound;   // [capC]
-  uint8_t* c_fl;     // [capC] bit0: FATPIPE
-};
-
+// (The mirror's layout, ResDev, is in lmm_dev.hpp: the context holds one.)
 constexpr uint8_t kResElemEnabled = 1;
 constexpr uint8_t kResCnstFatpipe = 1;
 

@@ -1,6 +1,6 @@
 // lmm_scan.hip — device-wide primitives for the resident flatten (lmm_resident_kernels.hpp): exclusive
 // prefix sums and a stable key/value radix sort, from hipCUB (rocPRIM underneath, tuned for gfx9).
-// Kept in their own translation unit so the hipCUB templates do not slow down lmm_hip.hip's build.
+// Kept in their own translation unit so the hipCUB templates do not slow down the driver units' build (lmm_hip*.hip).
 // Every call takes caller-owned scratch: `tmp`/`tmp_bytes` from a previous size query
 // (tmp == nullptr), as hipCUB does.
 #include <hip/hip_runtime.h>

@@ -22,29 +22,7 @@ enum : uint8_t { ACT_NO_CNST = 1, ACT_SUSPENDED = 2, ACT_NOT_STARTED = 4 };
 enum : uint8_t { HEAP_UNSET = 0, HEAP_LATENCY = 1, HEAP_MAX_DURATION = 2, HEAP_NORMAL = 3 };
 constexpr double kNoMaxDuration = -1.0;  // Action.hpp:17
 
-struct ActDev {
-  int64_t n;
-  const int32_t* vidx;     // dense variable index of each action's variable, -1 = not solved (value 0)
-  double* remains;
-  double* max_duration;
-  double* latency;
-  double* penalty;         // the variable's current penalty (finish test)
-  const double* share_pen; // CM02: sharing penalty restored once the latency is paid
-  const uint8_t* flags;    // ACT_NO_CNST, ACT_SUSPENDED
-  uint8_t* events;         // EV_* of the last update
-  unsigned long long* umin;  // next-event reduction (bit pattern of a non-negative double)
-  int32_t* nev;            // number of actions with an event in the last update
-  // LAZY update (lmmhip_actions_lazy_*): Action::last_update_ / last_value_ / start_time_ and the
-  // action's ActionHeap entry (date + type) — the heap itself is a min-reduction over `date`.
-  double* last_update;
-  double* last_value;
-  const double* start_time;
-  double* date;            // heap date (+inf when not in the heap)
-  uint8_t* htype;          // HEAP_*
-  int32_t* due;            // compacted due actions (lmmhip_actions_lazy_due)
-  int32_t* ndue;
-  int32_t* err;            // DIE_IMPOSSIBLE of next_occuring_event_lazy (Model.cpp:95-96)
-};
+// (The action state's layout, ActDev, is in lmm_dev.hpp: the context holds one.)
 
 __device__ __forceinline__ void double_update(double& v, double d, double prec) {
   v -= d;

@@ -8,7 +8,7 @@
 //   update_variable_penalty       maxmin.cpp:846-881
 //   var_free                      maxmin.cpp:106-138
 //   selective-update closure      maxmin.cpp:898-937 (iterative here: no recursion depth limit)
-// The solve itself runs on the GPU (lmm_hip.hip); this file only flattens and scatters.
+// The solve itself runs on the GPU (lmm_hip*.hip, lmm_ctx.hpp); this file only flattens and scatters.
 #include "lmm_system.hpp"
 
 #include <algorithm>

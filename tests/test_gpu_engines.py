@@ -254,7 +254,7 @@ def test_persistent_rendezvous_deadline_falls_back_fast():
     """A persistent solve whose grid cannot become co-resident — half the CUs held for 2 s by a kernel of another
     process (tests/c/occupy_run.py, tests/c/occupy.hip: the one-process-per-GPU deployment's neighbour) — closes
     its launch rendezvous after LMMHIP_PERSIST_RDV_MS (20 ms) and re-runs on the round engine on the free CUs
-    (lmm_persist_kernels.hpp bar_rdv, lmm_hip.hip solve_maxmin_persist): the values are the round engine's bytes,
+    (lmm_persist_kernels.hpp bar_rdv, lmm_hip_maxmin.hip solve_maxmin_persist): the values are the round engine's bytes,
     one fallback is counted, the solve returns well within the 2 s the CUs stay held (< 0.5 s), and the next solve
     of the context takes the round engine directly (cooldown) instead of waiting again."""
     import os
@@ -342,7 +342,7 @@ def _hint_steps(s, ids, step):
 
 @pytest.mark.parametrize("engine", [L.System.ENGINE_ROUNDS, L.System.ENGINE_FRONTIER])
 def test_round_hint_other_round_counts_bit_identical(engine):
-    """The chunked polls end a chunk where the previous solve of the context ended (round_hint_chunk, lmm_hip.hip):
+    """The chunked polls end a chunk where the previous solve of the context ended (round_hint_chunk, lmm_hip_maxmin.hip):
     a solve that takes more or fewer rounds than the previous one must still give a fresh context's bytes."""
     build = _synthetic(20000, 200000, 5, False)
     s = L.System(False)

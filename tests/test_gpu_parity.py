@@ -116,7 +116,8 @@ FB_FATPIPE_SEEDS = [0, 1, 3, 5, 6, 7, 9, 10, 12, 13, 15, 16, 17, 22, 23, 25, 30,
 
 @pytest.mark.parametrize("seed", range(20))
 @pytest.mark.parametrize("variant", ["fatpipe", "zero_bounds"])
-def test_random_fair_bottleneck_vs_oracle(seed, variant):
+def test_random_fair_bottleneck_vs_oracle(seed, variant, monkeypatch):
+    unpaced = seed < 5  # the first five seeds of each variant also run the polled rounds (LMMHIP_FB_PACE=0)
     if variant == "fatpipe":
         seed = FB_FATPIPE_SEEDS[seed]
     kw = dict(zero_bound_p=0.0, fatpipe_p=0.1) if variant == "fatpipe" else dict(zero_bound_p=0.05, fatpipe_p=0.0)
@@ -127,6 +128,15 @@ def test_random_fair_bottleneck_vs_oracle(seed, variant):
     os_.solve()
     worst, bad = K.compare_values(pvs, ovs)
     assert not bad, bad[:5]
+    if unpaced:  # the same system by the pipelined termination polls: the same bytes after the same rounds
+        qs, _, qvs = K.replay(L, ops, kind=L.System.FAIR_BOTTLENECK)
+        monkeypatch.setenv("LMMHIP_FB_PACE", "0")
+        qs.solve()
+        keys = sorted(pvs)
+        assert sorted(qvs) == keys
+        assert (np.array([qvs[k].get_value() for k in keys]).tobytes() ==
+                np.array([pvs[k].get_value() for k in keys]).tobytes())
+        assert qs.last_stats()["rounds"] == ps.last_stats()["rounds"]
 
 
 @pytest.mark.parametrize("kat", K.FB_TESH_KATS, ids=lambda f: f.__name__)
@@ -137,7 +147,10 @@ def test_fair_bottleneck_tesh_kats(kat):
     assert not K.check_fb_kat(expect)
 
 
-def test_fair_bottleneck_nonterminating_input_is_reported():
+@pytest.mark.parametrize("pace", ["default", "0"])
+def test_fair_bottleneck_nonterminating_input_is_reported(pace, monkeypatch):
+    if pace != "default":  # the pipelined termination polls instead of the progress words
+        monkeypatch.setenv("LMMHIP_FB_PACE", pace)
     s = L.System(False, L.System.FAIR_BOTTLENECK)
     z = s.constraint_new(None, 0.0)  # zero-bound: its variable leaves the list with mu = 0
     f = s.constraint_new(None, 5.0)

@@ -9,6 +9,7 @@ kernel of both engines and the batch kernel.
 import os
 import re
 import subprocess
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "simgrid_amd", "csrc")
@@ -16,10 +17,19 @@ HOT = ("mm_persist", "mm_vote_lane", "mm_vote", "mm_ready", "mm_saturate", "mm_u
        "mm_init_cnsts", "cmp_write", "fbk_", "fb_var_inc", "fr_")
 
 
-def resource_report():
-    out = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
-                          "-ffp-contract=off", "-c", "lmm_hip.hip", "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"],
+def makefile_units():
+    """The .hip translation units the Makefile builds and its HIPFLAGS (default ARCH, no EXTRA_HIPFLAGS)."""
+    mk = open(os.path.join(CSRC, "Makefile")).read().replace("\\\n", " ")
+    var = {k: v.strip() for k, v in re.findall(r"^(\w+) [:?]?= (.*)$", mk, re.M)}
+    flags = var["HIPFLAGS"].replace("$(ARCH)", var["ARCH"]).replace("$(EXTRA_HIPFLAGS)", "").split()
+    units = [u + ".hip" for u in re.findall(r"\$\(OUT\)/(\w+)\.o", var["OBJS"])
+             if os.path.exists(os.path.join(CSRC, u + ".hip"))]
+    return units, flags
+
+
+def unit_report(unit, flags):
+    out = subprocess.run(["/opt/rocm/bin/hipcc"] + flags + ["-c", unit, "-o", os.devnull,
+                                                           "-Rpass-analysis=kernel-resource-usage"],
                          cwd=CSRC, capture_output=True, text=True, check=True).stderr
     kernels, cur = {}, None
     for line in out.splitlines():
@@ -34,8 +44,23 @@ def resource_report():
     return kernels
 
 
+def resource_report():
+    """Merged report of every unit, and the kernel names more than one unit reports."""
+    units, flags = makefile_units()
+    assert "lmm_hip.hip" in units and "-ffp-contract=off" in flags, (units, flags)
+    with ThreadPoolExecutor(4) as ex:
+        reports = list(ex.map(lambda u: unit_report(u, flags), units))
+    kernels, twice = {}, []
+    for unit, rep in zip(units, reports):
+        twice += [(k, unit) for k in rep if k in kernels]
+        kernels.update(rep)
+    return kernels, twice
+
+
 def test_hot_kernels_do_not_spill():
-    kernels = resource_report()
+    kernels, twice = resource_report()
+    # every __global__ kernel is compiled in exactly one translation unit
+    assert not twice, twice
     hot = {k: v for k, v in kernels.items() if any(h in k for h in HOT)}
     assert any("mm_persist" in k for k in hot) and any("mm_saturate" in k for k in hot), sorted(kernels)
     # the report was parsed (a format change must not make this test pass vacuously)
