@@ -136,9 +136,15 @@ int lmmhip_flat_download(lmmhip_ctx* ctx, int64_t* counts3, uint32_t* var_ptr, i
 /* Declare the uploaded system a disjoint union of nsys independent systems (a parameter sweep, SURVEY.md
  * §8(a) C3): system i owns the dense variables [var_off[i], var_off[i+1]) and constraints
  * [cnst_off[i], cnst_off[i+1]) (offsets cover the system; checked on the device: no element may link two
- * systems).  A MAXMIN lmmhip_solve then runs one workgroup per system with the system in LDS
- * (lmm_batch_kernels.hpp) when the largest one fits (< 65535 variables / constraints / elements,
- * <= 64 KB of LDS), else the global engines.  nsys = 0 clears; every upload clears. */
+ * systems).  An lmmhip_solve of either kind then runs one workgroup per system with the system in LDS
+ * (MAXMIN: lmm_batch_kernels.hpp; FAIR_BOTTLENECK: lmm_fb_batch_kernels.hpp) when the largest one fits
+ * (< 65535 variables / constraints / elements, <= 64 KB of LDS), the context is not profiling and LMMHIP_BATCH
+ * is not 0, else the global engines.  nsys = 0 clears; every upload clears.
+ * FairBottleneck: every system's values are bit-identical to that system solved alone (and to the global
+ * engine on the union), and the rounds reported are the maximum over the systems.  The saturated set
+ * (lmmhip_get_saturated) and the work counters (lmmhip_fb_work) are per system, as if each were solved alone:
+ * the global engine on the union also erases a finished system's left-over constraints in a later round of
+ * the union and counts them once more, which the batch engine does not. */
 int lmmhip_set_batch(lmmhip_ctx* ctx, int64_t nsys, const int64_t* var_off, const int64_t* cnst_off);
 
 /* Solve on the device; values stay resident in HBM until lmmhip_get_values(). */
@@ -222,6 +228,16 @@ int lmmhip_ctx_set_engine(lmmhip_ctx* ctx, int engine);
  * engine directly.  Persistent launches of one process are serialised per device, so two Systems never starve
  * each other. */
 int lmmhip_engine_fallbacks(lmmhip_ctx* ctx, int64_t* n);
+/* The engine that ran the last successful lmmhip_solve of this context (LMMHIP_E_STATE before any): the
+ * max-min persistent / round / frontier engines (a persistent launch that fell back to the round engine reports
+ * ROUNDS), the max-min batch engine, FairBottleneck's chunked round engine, or its batch engine. */
+#define LMMHIP_RAN_PERSISTENT 0
+#define LMMHIP_RAN_ROUNDS 1
+#define LMMHIP_RAN_FRONTIER 2
+#define LMMHIP_RAN_BATCH 3
+#define LMMHIP_RAN_FB_ROUNDS 4
+#define LMMHIP_RAN_FB_BATCH 5
+int lmmhip_last_engine(lmmhip_ctx* ctx, int* engine);
 /* Round anatomy (diagnostic builds only: make EXTRA_HIPFLAGS=-DLMM_ANAT=1; scripts/anatomy.py): in the solves run
  * with LMMHIP_ANAT_ROUNDS="r0,r1,..." (at most 4 rounds) every wave of the round engine's vote, saturation and update
  * launches of those rounds writes a record of 20 words — entry and exit on the 100-MHz wall clock, its workgroup,

@@ -3,7 +3,7 @@
 //   lmm_hip.hip           context, flat allocation and upload, lmmhip_solve, setters, getters, profile exports;
 //                         owns lmm_common_kernels.hpp and lmm_cc_kernels.hpp
 //   lmm_hip_maxmin.hip    the round, frontier, persistent and batch max-min engines
-//   lmm_hip_fair.hip      FairBottleneck and its sharded protocol
+//   lmm_hip_fair.hip      FairBottleneck: the chunked engine, its sharded protocol, and the batch engine
 //   lmm_hip_resident.hip  the resident mirror, the device flatten and the value fetches
 //   lmm_hip_step.hip      the model-side action state
 //
@@ -146,8 +146,10 @@ void persist_ctx_ref(int device, int delta);
 constexpr unsigned kPersistProfCap = 1 << 16;  // barriers covered by lmmhip_persist_profile
 
 // block-diagonal batch (lmm_hip_maxmin.hip, lmmhip_set_batch)
+constexpr size_t kBatchLdsMax = 64 * 1024;  // LDS per workgroup; larger systems take the global engines
 bool batch_fits(const lmmhip_ctx* c);
 int solve_maxmin_batch(lmmhip_ctx* c, double prec);
+int batch_rounds_to_ctl(lmmhip_ctx* c, int grid);  // mm_batch_rounds: bt_rounds[0..grid) -> CTL_ROUNDS / CTL_ERR
 int engine_of(const lmmhip_ctx* c);
 
 // one-context FairBottleneck (lmm_hip_fair.hip solve_fair): the long shared constraints (fb_long_list) and the
@@ -157,6 +159,9 @@ struct FairEngine {
   bool perm_ok = false;
 };
 int solve_fair(lmmhip_ctx* c, double prec);
+// FairBottleneck of a declared batch (lmm_hip_fair.hip, lmm_fb_batch_kernels.hpp): one workgroup per system
+bool fb_batch_fits(const lmmhip_ctx* c);
+int solve_fair_batch(lmmhip_ctx* c, double prec);
 
 struct lmmhip_ctx {
   int device = 0;
@@ -183,6 +188,8 @@ struct lmmhip_ctx {
   std::vector<float> launch_ms;
   lmmhip_stats stats{};
   int last_kind = LMMHIP_KIND_MAXMIN;
+  int ran_engine = -1;   // LMMHIP_RAN_* of the solve in flight (set by the engine that runs it)
+  int last_engine = -1;  // ... of the last successful solve (lmmhip_last_engine); -1 = none yet
   double last_prec = 1e-5;  // precision of the last solve (lmmhip_get_saturated)
   bool solved = false;      // a solve completed since the last upload / flatten
   DevPtr<int32_t> vstat;    // profiling counters of mm_vote ([round][block] x 2)

@@ -14,6 +14,7 @@
 // with 10^6 elements (a CPU under thousands of flows, C5) spreads over the chip instead of
 // serialising one wave; per-chunk partials are combined per constraint in chunk order, so every
 // reduction is deterministic.
+// (A declared batch of small systems takes lmm_fb_batch_kernels.hpp instead: one workgroup per system, in LDS.)
 #pragma once
 #include "lmm_dev.hpp"
 

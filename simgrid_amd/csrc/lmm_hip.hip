@@ -530,7 +530,8 @@ int lmmhip_solve(lmmhip_ctx* c, int kind, double precision) {
   c->last_prec = precision;
   c->solved = false;
   c->ev1_done = false;
-  int rc = kind == LMMHIP_KIND_FAIR_BOTTLENECK ? solve_fair(c, precision)
+  int rc = kind == LMMHIP_KIND_FAIR_BOTTLENECK
+               ? (fb_batch_fits(c) ? solve_fair_batch(c, precision) : solve_fair(c, precision))
            : batch_fits(c)                             ? solve_maxmin_batch(c, precision)
            : engine_of(c) == LMMHIP_ENGINE_PERSISTENT ? solve_maxmin_persist(c, precision)
            : engine_of(c) == LMMHIP_ENGINE_FRONTIER   ? solve_maxmin_frontier(c, precision)
@@ -544,11 +545,21 @@ int lmmhip_solve(lmmhip_ctx* c, int kind, double precision) {
   HIPCHK(hipEventElapsedTime(&ms, c->ev0.p, c->ev1.p));
   c->stats.device_ms = ms;
   c->solved = true;
+  c->last_engine = c->ran_engine;
   c->stats.rounds = c->h_ctl.p[CTL_ROUNDS];
   if (kind == LMMHIP_KIND_MAXMIN && c->stats.rounds > 0)  // launched rounds include empty tail rounds
     c->stats.rounds = c->h_ctl.p[CTL_LASTR] + 1;
   if (c->profiling)
     return resolve_profile(c);
+  return 0;
+}
+
+int lmmhip_last_engine(lmmhip_ctx* c, int* engine) {
+  if (!c || !engine)
+    return fail(LMMHIP_E_ARG, "null argument");
+  if (c->last_engine < 0)
+    return fail(LMMHIP_E_STATE, "no solve has succeeded on this context yet");
+  *engine = c->last_engine;
   return 0;
 }
 

@@ -1,8 +1,10 @@
-// lmm_hip_fair.hip — FairBottleneck (lmmhip_solve's LMMHIP_KIND_FAIR_BOTTLENECK, lmm_ctx.hpp) and its sharded
-// protocol lmmhip_fb_shard_* (lmm_fb_kernels.hpp).
+// lmm_hip_fair.hip — FairBottleneck (lmmhip_solve's LMMHIP_KIND_FAIR_BOTTLENECK, lmm_ctx.hpp): the chunked engine
+// and its sharded protocol lmmhip_fb_shard_* (lmm_fb_kernels.hpp), and the batch engine of a declared
+// block-diagonal system (lmm_fb_batch_kernels.hpp).
 #include <chrono>
 
 #include "lmm_ctx.hpp"
+#include "lmm_fb_batch_kernels.hpp"
 #include "lmm_fb_kernels.hpp"
 #include "lmm_scan.hpp"
 
@@ -186,6 +188,7 @@ static int solve_fair_rounds(lmmhip_ctx* c, double prec) {
 }
 
 int solve_fair(lmmhip_ctx* c, double prec) {
+  c->ran_engine = LMMHIP_RAN_FB_ROUNDS;
   c->fb_shard = false;
   // shared constraints of at least this many elements get their increments precomputed element-parallel
   // (fbk_acc) and streamed into their chains (fb_chain); shorter ones compute them inside the chain
@@ -210,6 +213,65 @@ int solve_fair(lmmhip_ctx* c, double prec) {
   if (int rc = fb_perm(c))
     return rc;
   return solve_fair_rounds(c, prec);
+}
+
+// ---- block-diagonal batches: one workgroup per system, the system in LDS (lmm_fb_batch_kernels.hpp) ----
+// The conditions of batch_fits (lmm_hip_maxmin.hip), with this kernel's LDS layout.
+bool fb_batch_fits(const lmmhip_ctx* c) {
+  if (c->bt_n <= 0 || c->profiling)
+    return false;
+  if (const char* e = std::getenv("LMMHIP_BATCH"); e && *e == '0')
+    return false;
+  return c->bt_max_nv < 65535 && c->bt_max_nc < 65535 && c->bt_max_nnz < 65535 &&
+         fb_batch_lds_bytes(c->bt_max_nv, c->bt_max_nc, c->bt_max_nnz) <= kBatchLdsMax;
+}
+
+int solve_fair_batch(lmmhip_ctx* c, double prec) {
+  c->ran_engine = LMMHIP_RAN_FB_BATCH;
+  c->fb_shard = false;
+  size_t lds = fb_batch_lds_bytes(c->bt_max_nv, c->bt_max_nc, c->bt_max_nnz);
+  // both copies of the weights in LDS too when the budget allows (LMMHIP_FB_BATCH_WLDS=0: never; measurement)
+  const bool wl = lds + fb_batch_lds_weights(c->bt_max_nnz) <= kBatchLdsMax && env_int("LMMHIP_FB_BATCH_WLDS", 1);
+  if (wl)
+    lds += fb_batch_lds_weights(c->bt_max_nnz);
+  const void* kern = wl ? reinterpret_cast<const void*>(&fbk_batch_lds<true>)
+                        : reinterpret_cast<const void*>(&fbk_batch_lds<false>);
+  int per_cu = 0;
+  HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, int(kBatchLdsMax)));
+  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kFBB, lds));
+  int64_t grid = std::max<int64_t>(1, std::min<int64_t>(c->bt_n, int64_t(c->n_cu) * std::max(per_cu, 1)));
+  // LMMHIP_FB_BATCH_GRID=n: at most n workgroups (tests, measurement: several systems per workgroup's LDS)
+  if (const int cap = env_int("LMMHIP_FB_BATCH_GRID", 0); cap > 0)
+    grid = std::min<int64_t>(grid, cap);
+  if (grid > c->bt_cap) {
+    HIPCHK(c->bt_rounds.reset());
+    c->bt_cap = 0;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->bt_rounds.p), sizeof(int32_t) * size_t(grid)));
+    c->bt_cap = grid;
+  }
+  // the chunked engine's budget for this input (solve_fair_rounds): the union's sizes
+  const int64_t budget = 64 * (int64_t(c->d.nV) + int64_t(c->d.nC)) + 4096;
+  const int max_rounds = int(std::min<int64_t>(budget, INT32_MAX - 1));
+  Dev d = c->d;
+  if (wl)
+    hipLaunchKernelGGL(fbk_batch_lds<true>, dim3(unsigned(grid)), dim3(kFBB), lds, c->stream, d, c->bt_voff.p,
+                       c->bt_coff.p, c->bt_n, prec, c->bt_max_nv, c->bt_max_nc, c->bt_max_nnz, max_rounds,
+                       c->bt_rounds.p);
+  else
+    hipLaunchKernelGGL(fbk_batch_lds<false>, dim3(unsigned(grid)), dim3(kFBB), lds, c->stream, d, c->bt_voff.p,
+                       c->bt_coff.p, c->bt_n, prec, c->bt_max_nv, c->bt_max_nc, c->bt_max_nnz, max_rounds,
+                       c->bt_rounds.p);
+  HIPCHK(hipGetLastError());
+  c->stats.kernel_launches[2] += 1;
+  HIPCHK(hipEventRecord(c->ev1.p, c->stream));
+  c->ev1_done = true;
+  if (int rc = batch_rounds_to_ctl(c, int(grid)))  // CTL_ROUNDS = the maximum over the systems, CTL_ERR
+    return rc;
+  if (int rc = poll_ctl(c))
+    return rc;
+  if (c->h_ctl.p[CTL_ERR] == 2)
+    return fail(LMMHIP_E_NOCONVERGE, "batch fair-bottleneck round guard tripped");
+  return 0;
 }
 
 int lmmhip_fb_shard_owner(lmmhip_ctx* c, int64_t n_own, const int32_t* own_cnst, const int64_t* optr,

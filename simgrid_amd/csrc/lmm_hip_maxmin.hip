@@ -95,6 +95,7 @@ static int launch_vote(lmmhip_ctx* c, int64_t r, int64_t nrows) {
 // Slots: 0 mm_init_cnsts, 1 mm_init_vars, 2 mm_vote, 3 mm_ready, 4 mm_saturate, 5 mm_update,
 // 6 compaction.
 int solve_maxmin(lmmhip_ctx* c, double prec) {
+  c->ran_engine = LMMHIP_RAN_ROUNDS;
   Dev& d = c->d;
   struct RowofOff {  // the other engines never see the row map / row records (their compactions do not
     Dev& d;          // maintain them)
@@ -288,6 +289,7 @@ int solve_maxmin(lmmhip_ctx* c, double prec) {
 // constraints and the moving votes.  Slots: 2 fr_vote, 4 fr_sat (+ fr_sat_big), 5 fr_update, 6 the per-chunk
 // control-word copy; 0 / 1 init.
 int solve_maxmin_frontier(lmmhip_ctx* c, double prec) {
+  c->ran_engine = LMMHIP_RAN_FRONTIER;
   Dev d = c->d;  // (a copy: the frontier's buffers stay out of the context's Dev, which the other engines use)
   if (!c->vote_diag)  // per-round diagnostic counters only on request (LMMHIP_VOTE_DIAG): they cost atomics
     d.vstat = nullptr;
@@ -562,6 +564,7 @@ static int reap_retired_streams(lmmhip_ctx* c) {
 }
 
 int solve_maxmin_persist(lmmhip_ctx* c, double prec) {
+  c->ran_engine = LMMHIP_RAN_PERSISTENT;  // (solve_maxmin overwrites it when the solve falls back)
   if (int rc = reap_retired_streams(c))
     return rc;
   if (c->persist_cool > 0) {
@@ -581,8 +584,6 @@ int solve_maxmin_persist(lmmhip_ctx* c, double prec) {
 }
 
 // ---- block-diagonal batches: one workgroup per system, the system in LDS (lmm_batch_kernels.hpp) ----
-constexpr size_t kBatchLdsMax = 64 * 1024;  // per workgroup; larger systems take the global engines
-
 bool batch_fits(const lmmhip_ctx* c) {
   if (c->bt_n <= 0 || c->profiling)
     return false;
@@ -592,7 +593,14 @@ bool batch_fits(const lmmhip_ctx* c) {
          batch_lds_bytes(c->bt_max_nv, c->bt_max_nc, c->bt_max_nnz) <= kBatchLdsMax;
 }
 
+int batch_rounds_to_ctl(lmmhip_ctx* c, int grid) {
+  hipLaunchKernelGGL(mm_batch_rounds, dim3(1), dim3(kBlock), 0, c->stream, c->bt_rounds.p, grid, c->d.ctl);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 int solve_maxmin_batch(lmmhip_ctx* c, double prec) {
+  c->ran_engine = LMMHIP_RAN_BATCH;
   const size_t lds = batch_lds_bytes(c->bt_max_nv, c->bt_max_nc, c->bt_max_nnz);
   int per_cu = 0;
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mm_batch_lds),
@@ -612,8 +620,8 @@ int solve_maxmin_batch(lmmhip_ctx* c, double prec) {
   c->stats.kernel_launches[2] += 1;
   HIPCHK(hipEventRecord(c->ev1.p, c->stream));
   c->ev1_done = true;
-  hipLaunchKernelGGL(mm_batch_rounds, dim3(1), dim3(kBlock), 0, c->stream, c->bt_rounds.p, int(grid), d.ctl);
-  HIPCHK(hipGetLastError());
+  if (int rc = batch_rounds_to_ctl(c, int(grid)))
+    return rc;
   if (int rc = poll_ctl(c))
     return rc;
   if (c->h_ctl.p[CTL_ERR] == 2)

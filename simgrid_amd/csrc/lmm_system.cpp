@@ -1167,11 +1167,17 @@ void solve_batch(System** systems, int n) {
                           ordered ? f.csc_order.data() : nullptr);
   if (rc)
     fatal(std::string("batch upload failed: ") + lmmhip_last_error());
-  if (kind == SolverKind::MAXMIN && (rc = lmmhip_set_batch(s0->ctx(), n, voff.data(), coff.data())))
+  // both kinds have a batch engine (one workgroup per system); the device falls back to the global engines
+  // when the largest system does not fit
+  if ((rc = lmmhip_set_batch(s0->ctx(), n, voff.data(), coff.data())))
     fatal(std::string("batch declaration failed: ") + lmmhip_last_error());
   rc = lmmhip_solve(s0->ctx(), kind == SolverKind::FAIR_BOTTLENECK ? 1 : 0, maxmin_precision);
   if (rc)
     fatal(std::string("batch solve failed: ") + lmmhip_last_error());
+  lmmhip_stats st{};
+  lmmhip_get_stats(s0->ctx(), &st);
+  s0->set_batch_stats(st.rounds, st.device_ms, int64_t(f.dense_vars.size()), int64_t(f.cbound.size()),
+                      int64_t(f.cnst_idx.size()));
   std::vector<double> x(f.dense_vars.size());
   rc = lmmhip_get_values(s0->ctx(), x.data());
   if (rc)

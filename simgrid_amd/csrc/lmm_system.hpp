@@ -141,6 +141,14 @@ public:
   bool selective() const { return selective_; }
   SolverKind kind() const { return kind_; }
   const SolveStats& last_stats() const { return stats_; }
+  // solve_batch: the union's solve ran on this system's context (the first of the batch)
+  void set_batch_stats(int64_t rounds, double device_ms, int64_t n_var, int64_t n_cnst, int64_t nnz) {
+    stats_.rounds = rounds;
+    stats_.device_ms = device_ms;
+    stats_.n_var = n_var;
+    stats_.n_cnst = n_cnst;
+    stats_.nnz = nnz;
+  }
   // Lazy-mode side effect of lmm_solve (maxmin.cpp:536-538): actions of newly active elements.
   std::vector<Id>& modified_actions() { return modified_actions_; }
   void clear_modified_actions();

@@ -159,6 +159,7 @@ SIGNATURES = {
     "lmmhip_ctx_use_own_stream": (I, [P]),
     "lmmhip_ctx_set_engine": (I, [P, I]),
     "lmmhip_engine_fallbacks": (I, [P, PI64]),
+    "lmmhip_last_engine": (I, [P, PI]),
     "lmmhip_persist_profile": (I, [P, I, PI64, I64, PI64]),
     "lmmhip_persist_profile_blocks": (I, [P, PI64, I64, PI64, PI64]),
     "lmmhip_fb_shard_owner": (I, [P, I64, ct.POINTER(ct.c_int32), PI64, ct.POINTER(ct.c_int32), PD,
@@ -529,6 +530,16 @@ class System:
         n = ct.c_int64()
         _check_hip(lib().lmmhip_engine_fallbacks(self.device_ctx(), ct.byref(n)))
         return n.value
+
+    # lmmhip_last_engine's answers (include/lmm/lmm_hip.h, LMMHIP_RAN_*)
+    RAN_PERSISTENT, RAN_ROUNDS, RAN_FRONTIER, RAN_BATCH, RAN_FB_ROUNDS, RAN_FB_BATCH = range(6)
+
+    def last_engine(self):
+        """The engine that ran the last successful device solve of this system's context (lmmhip_last_engine): one
+        of the RAN_* constants.  After solve_batch(systems), ask the first system: its context ran the union."""
+        e = I()
+        _check_hip(lib().lmmhip_last_engine(self.device_ctx(), ct.byref(e)))
+        return e.value
 
     def device_values(self):
         """Values of the last solve in the device's dense (CSR) order (lmmhip_get_values)."""

@@ -216,16 +216,21 @@ def device_solve_flat(f, kind, precision=None, device=None):
 
 
 class DeviceBatch:
-    """Independent max-min systems (a parameter sweep) as ONE block-diagonal device
-    system: their flattened systems concatenated, uploaded once (lmmhip_upload) and declared a batch
-    (lmmhip_set_batch), so every solve() runs one workgroup per system with the system in LDS
-    (lmm_batch_kernels.hpp).  Inputs stay resident in HBM across solves."""
+    """Independent systems of one solver kind (a parameter sweep) as ONE block-diagonal device
+    system: their flattened systems concatenated, uploaded once and declared a batch (lmmhip_set_batch), so
+    every solve() runs one workgroup per system with the system in LDS (max-min: lmm_batch_kernels.hpp;
+    kind=FAIR_BOTTLENECK: lmm_fb_batch_kernels.hpp).  Inputs stay resident in HBM across solves.
+    FairBottleneck systems are uploaded with each system's element order (export_flat's csc_order, offset into
+    the concatenation: lmmhip_upload2), the order the reference subtracts a constraint's elements in."""
 
-    def __init__(self, systems, precision=None, device=None):
+    MAXMIN, FAIR_BOTTLENECK = 0, 1
+
+    def __init__(self, systems, precision=None, device=None, kind=MAXMIN):
         import torch
 
         L = lmm.lib()
         self.L = L
+        self.kind = int(kind)
         self.prec = lmm.get_precision() if precision is None else precision
         flats = [export_flat(s) for s in systems]
         nvs = np.array([len(f.penalty) for f in flats], np.int64)
@@ -250,9 +255,17 @@ class DeviceBatch:
             return a.ctypes.data_as(ct.POINTER(t))
 
         vp, ci, w, pen, vb, cb, cf = self.arrays
-        self._check(L.lmmhip_upload(self.ctx, self.n_var, self.n_cnst, self.nnz, p(vp, ct.c_int64),
-                                    p(ci, ct.c_int32), p(w, ct.c_double), p(pen, ct.c_double), p(vb, ct.c_double),
-                                    p(cb, ct.c_double), p(cf, ct.c_uint8)))
+        if self.kind == self.FAIR_BOTTLENECK:
+            order = np.ascontiguousarray(np.concatenate(
+                [csc_order_of(f) + eoff[i] for i, f in enumerate(flats)] + [np.empty(0, np.int64)]), np.int64)
+            self._check(L.lmmhip_upload2(self.ctx, self.n_var, self.n_cnst, self.nnz, p(vp, ct.c_int64),
+                                         p(ci, ct.c_int32), p(w, ct.c_double), p(pen, ct.c_double),
+                                         p(vb, ct.c_double), p(cb, ct.c_double), p(cf, ct.c_uint8),
+                                         p(order, ct.c_int64) if self.nnz else None))
+        else:
+            self._check(L.lmmhip_upload(self.ctx, self.n_var, self.n_cnst, self.nnz, p(vp, ct.c_int64),
+                                        p(ci, ct.c_int32), p(w, ct.c_double), p(pen, ct.c_double),
+                                        p(vb, ct.c_double), p(cb, ct.c_double), p(cf, ct.c_uint8)))
         self._check(L.lmmhip_set_batch(self.ctx, len(flats), p(self.var_off, ct.c_int64),
                                        p(self.cnst_off, ct.c_int64)))
 
@@ -261,7 +274,27 @@ class DeviceBatch:
             raise lmm.LmmError(self.L.lmmhip_last_error().decode())
 
     def solve(self):
-        self._check(self.L.lmmhip_solve(self.ctx, 0, self.prec))
+        self._check(self.L.lmmhip_solve(self.ctx, self.kind, self.prec))
+
+    def last_engine(self):
+        """The engine that ran the last solve (lmmhip_last_engine; lmm.System.RAN_*)."""
+        e = ct.c_int()
+        self._check(self.L.lmmhip_last_engine(self.ctx, ct.byref(e)))
+        return e.value
+
+    def fb_work(self):
+        """The last FairBottleneck solve's work summed over its rounds and systems (lmmhip_fb_work)."""
+        w = (ct.c_int64 * 3)()
+        self._check(self.L.lmmhip_fb_work(self.ctx, w))
+        return w[0], w[1], w[2]
+
+    def update_cnst_bounds(self, cbound):
+        """New bounds of every constraint (concatenated dense order; lmmhip_update_cnsts), for the next solve()."""
+        cb = np.ascontiguousarray(cbound, np.float64)
+        if len(cb) != self.n_cnst:
+            raise ValueError("one bound per constraint of the concatenated systems")
+        self._check(self.L.lmmhip_update_cnsts(self.ctx, cb.ctypes.data_as(ct.POINTER(ct.c_double))))
+        self.arrays = self.arrays[:5] + (cb,) + self.arrays[6:]
 
     def stats(self):
         st = lmm.LmmhipStats()
