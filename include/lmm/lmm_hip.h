@@ -139,7 +139,11 @@ int lmmhip_flat_download(lmmhip_ctx* ctx, int64_t* counts3, uint32_t* var_ptr, i
  * systems).  An lmmhip_solve of either kind then runs one workgroup per system with the system in LDS
  * (MAXMIN: lmm_batch_kernels.hpp; FAIR_BOTTLENECK: lmm_fb_batch_kernels.hpp) when the largest one fits
  * (< 65535 variables / constraints / elements, <= 64 KB of LDS), the context is not profiling and LMMHIP_BATCH
- * is not 0, else the global engines.  nsys = 0 clears; every upload clears.
+ * is not 0, else the global engines.  MAXMIN: every system has to fit by its own sizes; FAIR_BOTTLENECK: the
+ * largest counts of variables, constraints and elements, which may belong to different systems, have to fit
+ * together.  nsys = 0 clears; every upload clears.
+ * MAXMIN: a system's values do not depend on the other systems of the batch, on their order or on the number of
+ * workgroups (bit-identical); the rounds reported are the maximum over the systems.
  * FairBottleneck: every system's values are bit-identical to that system solved alone (and to the global
  * engine on the union), and the rounds reported are the maximum over the systems.  The saturated set
  * (lmmhip_get_saturated) and the work counters (lmmhip_fb_work) are per system, as if each were solved alone:
@@ -153,7 +157,9 @@ int lmmhip_solve(lmmhip_ctx* ctx, int kind, double precision);
 /* Copy the solved values (n_var doubles, CSR variable order) to host memory. */
 int lmmhip_get_values(lmmhip_ctx* ctx, double* values_out);
 /* Per variable of the last max-min solve (dense order, as lmmhip_get_values): 1 + the device round that fixed or
- * dropped it (0: never; measurement — the dependency-depth comparison of scripts/depth.py). */
+ * dropped it (0: never; measurement — the dependency-depth comparison of scripts/depth.py).  The global engines
+ * record it; after a solve that ran the batch engine (lmmhip_last_engine: LMMHIP_RAN_BATCH), which keeps its rounds
+ * in LDS, the call fails with LMMHIP_E_STATE. */
 int lmmhip_get_var_rounds(lmmhip_ctx* ctx, int32_t* rounds_out);
 /* Saturated set of the last solve, one byte per constraint of the solved system (dense order):
  *   MAXMIN: sat(c) = NOT double_positive(bound - U_c, bound * precision), U_c = Constraint::get_usage()

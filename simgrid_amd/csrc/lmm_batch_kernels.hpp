@@ -26,7 +26,7 @@ constexpr int kBB = 256;  // threads per workgroup
 constexpr int kG = 4;     // lanes per variable (vote, saturation) and per constraint (ready test)
 constexpr int kSatW = 4;  // weights per lane prefetched by the saturation (rows up to kG * kSatW elements)
 
-// LDS bytes of a workgroup for systems of at most nv variables, nc constraints and nnz elements
+// LDS bytes of a workgroup laid out for nv variables, nc constraints and nnz elements
 __host__ __device__ inline size_t batch_lds_bytes(int nv, int nc, int nnz) {
   size_t b = sizeof(double) * (4 * size_t(nc) + 3 * size_t(nv)) +                 // cnst / var state
              sizeof(unsigned long long) * 3 * size_t(nc) +                         // decrement records
@@ -36,34 +36,40 @@ __host__ __device__ inline size_t batch_lds_bytes(int nv, int nc, int nnz) {
   return (b + 15) / 16 * 16;
 }
 
+// The LDS layout follows the batch's largest counts of variables, constraints and elements (kOwn = false: the
+// offsets are the same for every system of the launch) when an allocation for the three together fits the
+// budget.  They may belong to different systems, each of which fits alone: then every system is laid out by its own
+// sizes (kOwn = true; the launch allocates the largest member's need), a small one in the low part of the allocation.
+template <bool kOwn>
 __global__ void __launch_bounds__(kBB, 8) mm_batch_lds(Dev s, const int64_t* __restrict__ var_off,
                                                    const int64_t* __restrict__ cnst_off, int64_t nsys, double prec,
                                                    int max_nv, int max_nc, int max_nnz, int32_t* block_rounds) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  double* c_rem = reinterpret_cast<double*>(lds);
-  double* c_use = c_rem + max_nc;
-  double* c_rat = c_use + max_nc;
-  double* c_bnd = c_rat + max_nc;
-  double* v_x = c_bnd + max_nc;
-  double* v_pen = v_x + max_nv;
-  double* v_vb = v_pen + max_nv;
-  unsigned long long* c_q = reinterpret_cast<unsigned long long*>(v_vb + max_nv);  // [3 * max_nc]
-  int32_t* c_exp = reinterpret_cast<int32_t*>(c_q + 3 * max_nc);
-  uint16_t* l_vp = reinterpret_cast<uint16_t*>(c_exp + max_nc);  // [max_nv + 1] CSR offsets
-  uint16_t* l_cp = l_vp + (max_nv + 1);                           // [max_nc + 1] CSC offsets
-  uint16_t* l_cc = l_cp + (max_nc + 1);                           // [max_nnz] CSR local constraint
-  uint16_t* l_cv = l_cc + max_nnz;                                // [max_nnz] CSC local variable
-  uint16_t* v_vote = l_cv + max_nnz;                              // [max_nv]
-  uint8_t* c_st = reinterpret_cast<uint8_t*>(v_vote + max_nv);    // 0 live, 1 out
-  uint8_t* c_fl = c_st + max_nc;                                  // FATPIPE
-  uint8_t* c_nr = c_fl + max_nc;  // 1 = blocked this round: a live variable on it votes elsewhere or hit its bound
-  uint8_t* v_st = c_nr + max_nc;  // 0 live, 1 done
   int rounds_max = 0;
   for (int64_t sy = blockIdx.x; sy < nsys; sy += gridDim.x) {
     const int64_t vb = var_off[sy], cb = cnst_off[sy];
     const int nv = int(var_off[sy + 1] - vb), nc = int(cnst_off[sy + 1] - cb);
     const uint32_t eb = s.var_ptr[vb], kb = s.cnst_ptr[cb];
     const int ne = int(s.var_ptr[vb + nv] - eb);
+    const int lv = kOwn ? nv : max_nv, lc = kOwn ? nc : max_nc, le = kOwn ? ne : max_nnz;
+    double* c_rem = reinterpret_cast<double*>(lds);  // (the layout batch_lds_bytes(lv, lc, le) counts)
+    double* c_use = c_rem + lc;
+    double* c_rat = c_use + lc;
+    double* c_bnd = c_rat + lc;
+    double* v_x = c_bnd + lc;
+    double* v_pen = v_x + lv;
+    double* v_vb = v_pen + lv;
+    unsigned long long* c_q = reinterpret_cast<unsigned long long*>(v_vb + lv);  // [3 * lc]
+    int32_t* c_exp = reinterpret_cast<int32_t*>(c_q + 3 * lc);
+    uint16_t* l_vp = reinterpret_cast<uint16_t*>(c_exp + lc);  // [lv + 1] CSR offsets
+    uint16_t* l_cp = l_vp + (lv + 1);                           // [lc + 1] CSC offsets
+    uint16_t* l_cc = l_cp + (lc + 1);                           // [le] CSR local constraint
+    uint16_t* l_cv = l_cc + le;                                 // [le] CSC local variable
+    uint16_t* v_vote = l_cv + le;                               // [lv]
+    uint8_t* c_st = reinterpret_cast<uint8_t*>(v_vote + lv);    // 0 live, 1 out
+    uint8_t* c_fl = c_st + lc;                                  // FATPIPE
+    uint8_t* c_nr = c_fl + lc;  // 1 = blocked this round: a live variable on it votes elsewhere or hit its bound
+    uint8_t* v_st = c_nr + lc;  // 0 live, 1 done
     // ---- stage the system ----
     for (int i = threadIdx.x; i <= nv; i += kBB)
       l_vp[i] = uint16_t(s.var_ptr[vb + i] - eb);

@@ -219,6 +219,7 @@ struct lmmhip_ctx {
   DevPtr<int64_t> bt_voff, bt_coff;
   DevPtr<int32_t> bt_rounds;  // [grid] rounds of each workgroup's systems
   int bt_max_nv = 0, bt_max_nc = 0, bt_max_nnz = 0;
+  size_t bt_lds = 0;  // mm_batch_lds' LDS bytes: the largest batch_lds_bytes over the systems, each by its own sizes
   int64_t bt_cap = 0;
   // fair bottleneck round state (lmmhip_solve and the sharded lmmhip_fb_shard_* protocol)
   int64_t fb_round = 0;

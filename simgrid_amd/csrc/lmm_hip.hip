@@ -813,6 +813,8 @@ int lmmhip_get_values(lmmhip_ctx* c, double* out) {
 int lmmhip_get_var_rounds(lmmhip_ctx* c, int32_t* out) {
   if (!c || !c->solved || c->last_kind != LMMHIP_KIND_MAXMIN)
     return fail(LMMHIP_E_STATE, "no max-min solve to read rounds from");
+  if (c->last_engine == LMMHIP_RAN_BATCH)  // mm_batch_lds keeps its rounds in LDS: vstate is not written
+    return fail(LMMHIP_E_STATE, "the batch engine ran the last max-min solve: it records no per-variable rounds");
   if (!out && c->d.nV)
     return fail(LMMHIP_E_ARG, "null output");
   HIPCHK(hipSetDevice(c->device));

@@ -589,8 +589,8 @@ bool batch_fits(const lmmhip_ctx* c) {
     return false;
   if (const char* e = std::getenv("LMMHIP_BATCH"); e && *e == '0')
     return false;
-  return c->bt_max_nv < 65535 && c->bt_max_nc < 65535 && c->bt_max_nnz < 65535 &&
-         batch_lds_bytes(c->bt_max_nv, c->bt_max_nc, c->bt_max_nnz) <= kBatchLdsMax;
+  // (every member has to fit alone: solve_maxmin_batch lays the LDS out for each system by its own sizes if need be)
+  return c->bt_max_nv < 65535 && c->bt_max_nc < 65535 && c->bt_max_nnz < 65535 && c->bt_lds <= kBatchLdsMax;
 }
 
 int batch_rounds_to_ctl(lmmhip_ctx* c, int grid) {
@@ -601,21 +601,31 @@ int batch_rounds_to_ctl(lmmhip_ctx* c, int grid) {
 
 int solve_maxmin_batch(lmmhip_ctx* c, double prec) {
   c->ran_engine = LMMHIP_RAN_BATCH;
-  const size_t lds = batch_lds_bytes(c->bt_max_nv, c->bt_max_nc, c->bt_max_nnz);
+  // one layout for the launch when the batch's largest counts fit together, else every system by its own sizes
+  const size_t lds_max = batch_lds_bytes(c->bt_max_nv, c->bt_max_nc, c->bt_max_nnz);
+  const bool own = lds_max > kBatchLdsMax;
+  const size_t lds = own ? c->bt_lds : lds_max;
+  const void* kern = own ? reinterpret_cast<const void*>(&mm_batch_lds<true>)
+                         : reinterpret_cast<const void*>(&mm_batch_lds<false>);
   int per_cu = 0;
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mm_batch_lds),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, int(kBatchLdsMax)));
-  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&mm_batch_lds), kBB,
-                                                      lds));
-  const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(c->bt_n, int64_t(c->n_cu) * std::max(per_cu, 1)));
+  HIPCHK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, int(kBatchLdsMax)));
+  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kBB, lds));
+  int64_t grid = std::max<int64_t>(1, std::min<int64_t>(c->bt_n, int64_t(c->n_cu) * std::max(per_cu, 1)));
+  // LMMHIP_BATCH_GRID=n: at most n workgroups (tests, measurement: several systems per workgroup's LDS)
+  if (const int cap = env_int("LMMHIP_BATCH_GRID", 0); cap > 0)
+    grid = std::min<int64_t>(grid, cap);
   if (grid > c->bt_cap) {
     HIPCHK(c->bt_rounds.reset());
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&c->bt_rounds.p), sizeof(int32_t) * size_t(grid)));
     c->bt_cap = grid;
   }
   Dev d = c->d;
-  hipLaunchKernelGGL(mm_batch_lds, dim3(unsigned(grid)), dim3(kBB), lds, c->stream, d, c->bt_voff.p, c->bt_coff.p,
-                     c->bt_n, prec, c->bt_max_nv, c->bt_max_nc, c->bt_max_nnz, c->bt_rounds.p);
+  if (own)
+    hipLaunchKernelGGL(mm_batch_lds<true>, dim3(unsigned(grid)), dim3(kBB), lds, c->stream, d, c->bt_voff.p,
+                       c->bt_coff.p, c->bt_n, prec, c->bt_max_nv, c->bt_max_nc, c->bt_max_nnz, c->bt_rounds.p);
+  else
+    hipLaunchKernelGGL(mm_batch_lds<false>, dim3(unsigned(grid)), dim3(kBB), lds, c->stream, d, c->bt_voff.p,
+                       c->bt_coff.p, c->bt_n, prec, c->bt_max_nv, c->bt_max_nc, c->bt_max_nnz, c->bt_rounds.p);
   HIPCHK(hipGetLastError());
   c->stats.kernel_launches[2] += 1;
   HIPCHK(hipEventRecord(c->ev1.p, c->stream));
@@ -648,10 +658,15 @@ int lmmhip_set_batch(lmmhip_ctx* c, int64_t nsys, const int64_t* var_off, const 
   HIPCHK(hipMemcpyAsync(vp.data(), d.var_ptr, vp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   int64_t mv = 0, mc = 0, me = 0;
+  size_t lds = 0;  // the max-min batch kernel's need: the largest over the systems, each by its own sizes
   for (int64_t i = 0; i < nsys; i++) {
-    mv = std::max(mv, var_off[i + 1] - var_off[i]);
-    mc = std::max(mc, cnst_off[i + 1] - cnst_off[i]);
-    me = std::max(me, int64_t(vp[size_t(var_off[i + 1])]) - int64_t(vp[size_t(var_off[i])]));
+    const int64_t nv = var_off[i + 1] - var_off[i], nc = cnst_off[i + 1] - cnst_off[i];
+    const int64_t ne = int64_t(vp[size_t(var_off[i + 1])]) - int64_t(vp[size_t(var_off[i])]);
+    mv = std::max(mv, nv);
+    mc = std::max(mc, nc);
+    me = std::max(me, ne);
+    if (nv < 65535 && nc < 65535 && ne < 65535)  // (larger ones: no batch engine, batch_fits)
+      lds = std::max(lds, batch_lds_bytes(int(nv), int(nc), int(ne)));
   }
   HIPCHK(c->bt_voff.reset());
   HIPCHK(c->bt_coff.reset());
@@ -672,5 +687,6 @@ int lmmhip_set_batch(lmmhip_ctx* c, int64_t nsys, const int64_t* var_off, const 
   c->bt_max_nv = int(mv);
   c->bt_max_nc = int(mc);
   c->bt_max_nnz = int(me);
+  c->bt_lds = lds;
   return 0;
 }
