@@ -196,7 +196,7 @@ struct Dev {
   int32_t* hprog;
   int32_t* vstat;   // profiling only (else null): [round][block] re-evaluated rows / elements
   // round anatomy (diagnostic build LMM_ANAT=1 only, else null): per-wave stamps of the round engine's kernels in
-  // the rounds anat_r[0..kAnatSlots) (lmm_anat below)
+  // the rounds anat_r[0..kAnatSlots) (the Anat probe below)
   unsigned long long* anat;
   int32_t anat_r[4];
 };
@@ -383,13 +383,21 @@ inline int grid_for(int64_t n, int per_block) {
 }
 
 // ---- round anatomy (diagnostic build only: LMM_ANAT=1, scripts/anatomy.py) ----
-// In the rounds named by Dev::anat_r, every wave of mm_vote_lane / mm_saturate_q / mm_update writes one record of
-// kAnatFields words into anat[((slot * kAnatKernels + kernel) * kAnatWaves + wave) * kAnatFields]: its entry and exit on the
-// 100-MHz wall clock (s_memrealtime, one clock for the whole chip), its workgroup, and the time it spent at each
-// dependent level of its work (the clock read waits for the level's loaded values, so a level's time is from the
-// previous stamp to the arrival of that level's data).  The stamps serialise what the real kernel overlaps: read
-// the SHARES of a round, not the stamped build's length (cdna_hip_programming.md §7, in-kernel stamps).  In the
-// product build (LMM_ANAT=0) none of this is compiled.
+// In the rounds named by Dev::anat_r, every wave of mm_vote_lane / mm_saturate_q / mm_update (and of fr_vote / fr_sat /
+// fr_sat_big / fr_update) writes one record of kAnatFields words into
+// anat[((slot * kAnatKernels + kernel) * kAnatWaves + wave) * kAnatFields]: its entry and exit on the 100-MHz wall
+// clock (s_memrealtime, one clock for the whole chip), its workgroup, and the time it spent at each dependent level of
+// its work (the clock read waits for the level's loaded values, so a level's time is from the previous stamp to the
+// arrival of that level's data).  The stamps serialise what the real kernel overlaps: read the SHARES of a round, not
+// the stamped build's length (cdna_hip_programming.md §7, in-kernel stamps).
+//
+// The kernels speak to one probe type, the same in both builds.  A kernel keeps an AnatWave (the wave's record
+// pointer, level accumulators with the running stamp, work counters) and opens it for (s, round, kernel); that gives
+// an Anat, a by-value handle the helpers take as an ordinary trailing parameter.  A default Anat is closed: every
+// operation on it does nothing and reads 0 (callers outside the stamped kernels pass none).  What only the stamps
+// need (sums that make a level wait for its loads, ballot counts, the record's stores) stands under `if (an.on())`.
+// In the product build (LMM_ANAT=0) both types are empty, every member is an empty inline and on() is a constant
+// false, so none of it reaches the code.  This is the only file whose preprocessor lines name LMM_ANAT.
 #ifndef LMM_ANAT
 #define LMM_ANAT 0
 #endif
@@ -399,6 +407,13 @@ constexpr int kAnatFields = 20;
 constexpr int kAnatWaves = 8192;
 // the round engine's vote / saturation / update; the frontier engine's fr_vote / fr_sat / fr_update / fr_sat_big
 enum : int { ANAT_VOTE = 0, ANAT_SAT = 1, ANAT_UPD = 2, ANAT_SATB = 3 };
+// (a level of the wave's slowest lane)
+__device__ __forceinline__ unsigned anat_wmax(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+    v = max(v, (unsigned)__shfl_xor(int(v), o, kWave));
+  return v;
+}
 #if LMM_ANAT
 __device__ __forceinline__ unsigned long long anat_now() {
   unsigned long long t;
@@ -406,29 +421,11 @@ __device__ __forceinline__ unsigned long long anat_now() {
   return t;
 }
 // the clock read after `v` has arrived (a use of its register)
-template <class T> __device__ __forceinline__ void anat_use(const T& v) {
+template <class T> __device__ __forceinline__ void anat_use(T v) {
   if constexpr (sizeof(T) == 8)
     asm volatile("" : : "v"(v) : "memory");
   else
     asm volatile("" : : "v"(uint32_t(v)) : "memory");
-}
-// per-wave accumulators of the dependent levels (registers; a field per level), and the running stamp
-struct AnatAcc {
-  unsigned lv[10];
-  unsigned long long at;
-};
-#define ANAT_LVL(aa, i, dep)                      \
-  do {                                            \
-    anat_use(dep);                                \
-    const unsigned long long t_ = anat_now();     \
-    (aa).lv[i] += unsigned(t_ - (aa).at);         \
-    (aa).at = t_;                                 \
-  } while (0)
-__device__ __forceinline__ unsigned anat_wmax(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-    v = max(v, (unsigned)__shfl_xor(int(v), o, kWave));
-  return v;
 }
 __device__ __forceinline__ int anat_slot(const Dev& s, int round) {
   if (!s.anat)
@@ -444,6 +441,66 @@ __device__ __forceinline__ unsigned long long* anat_rec(const Dev& s, int slot, 
     return nullptr;
   return s.anat + ((int64_t(slot) * kAnatKernels + kernel) * kAnatWaves + wave) * kAnatFields;
 }
+struct AnatWave;
+struct Anat {
+  AnatWave* w = nullptr;
+  __device__ __forceinline__ bool on() const { return w != nullptr; }
+  __device__ __forceinline__ unsigned long long now() const { return w ? anat_now() : 0; }
+  __device__ __forceinline__ unsigned long long restart() const;                  // the running stamp := now
+  template <class T> __device__ __forceinline__ void level(int i, T dep) const;   // lv[i] += now (after dep) - stamp
+  __device__ __forceinline__ void count(int k, unsigned n = 1) const;             // wc[k] += n
+  __device__ __forceinline__ unsigned lv(int i) const;
+  __device__ __forceinline__ unsigned cnt(int k) const;
+  __device__ __forceinline__ void put(int i, unsigned long long v) const;         // word i of the wave's record
+};
+struct AnatWave {
+  unsigned long long* rec;  // the wave's record, null outside the stamped rounds
+  unsigned lv[10];          // per-wave accumulators of the dependent levels (registers; a field per level)
+  unsigned long long at;    //   and the running stamp
+  unsigned wc[4];           // work counters
+  __device__ __forceinline__ Anat open(const Dev& s, int round, int kernel) {
+    *this = AnatWave{};
+    rec = anat_rec(s, anat_slot(s, round), kernel);
+    return Anat{rec ? this : nullptr};
+  }
+};
+__device__ __forceinline__ unsigned long long Anat::restart() const {
+  if (!w)
+    return 0;
+  return w->at = anat_now();
+}
+template <class T> __device__ __forceinline__ void Anat::level(int i, T dep) const {
+  if (w) {
+    anat_use(dep);
+    const unsigned long long t = anat_now();
+    w->lv[i] += unsigned(t - w->at);
+    w->at = t;
+  }
+}
+__device__ __forceinline__ void Anat::count(int k, unsigned n) const {
+  if (w)
+    w->wc[k] += n;
+}
+__device__ __forceinline__ unsigned Anat::lv(int i) const { return w ? w->lv[i] : 0u; }
+__device__ __forceinline__ unsigned Anat::cnt(int k) const { return w ? w->wc[k] : 0u; }
+__device__ __forceinline__ void Anat::put(int i, unsigned long long v) const {
+  if (w)
+    w->rec[i] = v;
+}
+#else
+struct Anat {
+  static constexpr bool on() { return false; }
+  __device__ __forceinline__ unsigned long long now() const { return 0; }
+  __device__ __forceinline__ unsigned long long restart() const { return 0; }
+  template <class T> __device__ __forceinline__ void level(int, T) const {}
+  __device__ __forceinline__ void count(int, unsigned = 1) const {}
+  __device__ __forceinline__ unsigned lv(int) const { return 0; }
+  __device__ __forceinline__ unsigned cnt(int) const { return 0; }
+  __device__ __forceinline__ void put(int, unsigned long long) const {}
+};
+struct AnatWave {
+  __device__ __forceinline__ Anat open(const Dev&, int, int) { return Anat{}; }
+};
 #endif
 
 }  // namespace lmmdev

@@ -140,25 +140,10 @@ __device__ __forceinline__ uint32_t row_floor32(uint32_t sk, uint32_t mk, double
   return fl <= mk ? 0u : fl;
 }
 
-// (LMM_ANAT: `an` = the dependent levels into ar->lv: 1 row (csr_cs) + bound / penalty, 2 keys + floors, 3 the rest of
-// the row + exact ratios, 4 the vote's stores and atomics issued)
+// (an: the dependent levels: lv[1] row (csr_cs) + bound / penalty, lv[2] keys + floors, lv[3] the rest of the row +
+// exact ratios, lv[4] the vote's stores and atomics issued)
 template <int R, bool kMinfl = true, bool kEarly = true>
-__device__ __forceinline__ int fr_revote(const Dev& s, int v, int t, uint32_t b, uint32_t e, int round
-#if LMM_ANAT
-                                         , bool an = false, AnatAcc* ar = nullptr
-#endif
-) {
-#if LMM_ANAT
-#define FV_LVL(i, dep)       \
-  do {                       \
-    if (an)                  \
-      ANAT_LVL(*ar, i, dep); \
-  } while (0)
-#else
-#define FV_LVL(i, dep) \
-  do {                 \
-  } while (0)
-#endif
+__device__ __forceinline__ int fr_revote(const Dev& s, int v, int t, uint32_t b, uint32_t e, int round, Anat an) {
   const uint32_t* __restrict__ key = s.key32;
   // (a queued variable is alive: votes are registered only by alive variables, and the slot of a variable
   // fixed since — at its bound, by fr_revote — was cleared when it was queued)
@@ -172,30 +157,26 @@ __device__ __forceinline__ int fr_revote(const Dev& s, int v, int t, uint32_t b,
     cc[i] = x.x;
     sl[i] = uint32_t(x.y);
   }
-#if LMM_ANAT
-  if (an) {
+  if (an.on()) {
     int sc = 0;
 #pragma unroll
     for (int i = 0; i < R; i++)
       sc += cc[i] + int(sl[i]);
-    FV_LVL(1, vb + p + double(sc));
+    an.level(1, vb + p + double(sc));
   }
-#endif
   uint32_t kk[R], mf[R];  // keys and registered floors of the row's constraints, their loads in flight together
 #pragma unroll
   for (int i = 0; i < R; i++) {
     kk[i] = cc[i] >= 0 ? key[cc[i]] : kDead32;
     mf[i] = kMinfl && kEarly && cc[i] >= 0 ? s.minfl[cc[i]] : 0u;
   }
-#if LMM_ANAT
-  if (an) {
+  if (an.on()) {
     uint32_t sk0 = 0;
 #pragma unroll
     for (int i = 0; i < R; i++)
       sk0 += kk[i] + mf[i];
-    FV_LVL(2, sk0);
+    an.level(2, sk0);
   }
-#endif
   uint32_t mk = kDead32;
 #pragma unroll
   for (int i = 0; i < R; i++)
@@ -256,7 +237,7 @@ __device__ __forceinline__ int fr_revote(const Dev& s, int v, int t, uint32_t b,
       }
     }
   }
-  FV_LVL(3, minr + double(newt + nmin));
+  an.level(3, minr + double(newt + nmin));
   if (vb > 0 && vb * p < minr) {  // fixed at its bound (maxmin.cpp:587-589)
     s.vstate[v] = round + 1;
     s.x[v] = vb;
@@ -299,21 +280,21 @@ __device__ __forceinline__ int fr_revote(const Dev& s, int v, int t, uint32_t b,
   if (kMinfl && fl < mfn)
     atomicMin(&s.minfl[newt], fl);
   if (newt == t) {
-    FV_LVL(4, 0u);
+    an.level(4, 0u);
     return FR_STAY;
   }
   if (t >= 0 && kt != kDead32)
     atomicAdd(&s.nvote[t], mult_old);
   atomicSub(&s.nvote[newt], mult_new);
   s.rtgt[0][v] = newt;
-  FV_LVL(4, 0u);
+  an.level(4, 0u);
   return FR_MOVE;
 }
 
 // Round 0: every variable votes (the floors' per-constraint minima come after, from fr_minfl_all).
 __global__ void __launch_bounds__(kBlock) fr_vote_all(Dev s) {
   for (int64_t v = int64_t(blockIdx.x) * kBlock + threadIdx.x; v < s.nV; v += int64_t(gridDim.x) * kBlock)
-    fr_revote<8, false>(s, int(v), kUnvoted, s.var_ptr[v], s.var_ptr[v + 1], 0);
+    fr_revote<8, false>(s, int(v), kUnvoted, s.var_ptr[v], s.var_ptr[v + 1], 0, Anat());
 }
 
 // After round 0's vote: minfl[c] = min of the floors registered in c's slots, 16 lanes per constraint (four
@@ -342,14 +323,10 @@ __global__ void __launch_bounds__(kBlock) fr_minfl_all(Dev s) {
 
 // Rounds >= 1: the variables fr_update queued in workgroup b's segment (the CSC range of its constraints).
 // Also the termination test (maxmin.cpp:680): no constraint alive after the last update -> CTL_DONE.
-// fr_vote_blk: the work of workgroup vb.
+// fr_vote_blk: the work of workgroup vb (an: lv[0] the queue counts; counters 0 queued rows of the workgroup, 1 this
+// lane's re-votes; ar: lv[0] a queue entry, then fr_revote's levels).
 template <int R>
-__device__ __forceinline__ void fr_vote_blk(const Dev& s, int round, int spb, int vb
-#if LMM_ANAT
-                                            , bool an = false, AnatAcc* aa = nullptr, AnatAcc* ar = nullptr,
-                                            unsigned* wc = nullptr
-#endif
-) {
+__device__ __forceinline__ void fr_vote_blk(const Dev& s, int round, int spb, int vb, Anat an, Anat ar) {
   // spb (<= kFVS) consecutive segments per workgroup: on C2 ~170 queued rows, one pass, and the launch's
   // workgroups resident at once; small systems keep one segment per workgroup (more workgroups)
   const int64_t nseg = (int64_t(s.nC) + kFB - 1) / kFB;
@@ -363,34 +340,20 @@ __device__ __forceinline__ void fr_vote_blk(const Dev& s, int round, int spb, in
     seg[k] = k < spb && sg < nseg ? s.cnst_ptr[sg * kFB] : 0u;
     pre[k + 1] = pre[k] + n[k];
   }
-#if LMM_ANAT
-  if (an) {
-    ANAT_LVL(*aa, 0, pre[kFVS] + int(seg[0]));
-    wc[0] = unsigned(pre[kFVS]);
-  }
-#endif
+  an.level(0, pre[kFVS] + int(seg[0]));
+  an.count(0, unsigned(pre[kFVS]));
   for (int i = threadIdx.x; i < pre[kFVS]; i += kFB) {
     int k = 0;
 #pragma unroll
     for (int q = 1; q < kFVS; q++)
       k += i >= pre[q];
     const uint32_t at = seg[k] + uint32_t(i - pre[k]);
-#if LMM_ANAT
-    if (an) {
-      ar->at = anat_now();
-      wc[1]++;
-    }
-#endif
+    ar.restart();
+    an.count(1);
     const unsigned long long a = s.fq_a[at], rw = s.fq_b[at];
-#if LMM_ANAT
-    if (an)
-      ANAT_LVL(*ar, 0, a + rw);
+    ar.level(0, a + rw);
     const int o = fr_revote<R, true, false>(s, int(uint32_t(a)), int(uint32_t(a >> 32)), uint32_t(rw),
-                                             uint32_t(rw >> 32), round, an, ar);
-#else
-    const int o = fr_revote<R, true, false>(s, int(uint32_t(a)), int(uint32_t(a >> 32)), uint32_t(rw),
-                                             uint32_t(rw >> 32), round);
-#endif
+                                             uint32_t(rw >> 32), round, ar);
     if (s.vstat) {
       fr_diag(s, round, 6, true);
       fr_diag(s, round, 4, o == FR_MOVE);
@@ -400,14 +363,9 @@ __device__ __forceinline__ void fr_vote_blk(const Dev& s, int round, int spb, in
 }
 
 template <int R = 8> __global__ void __launch_bounds__(kFB) fr_vote(Dev s, int round, int spb) {
-#if LMM_ANAT
-  unsigned long long* arec = anat_rec(s, anat_slot(s, round), ANAT_VOTE);
-  const bool an = arec != nullptr;
-  AnatAcc aa{}, ar{};
-  unsigned wc[2] = {0, 0};  // queued rows of the workgroup, this lane's re-votes
-  const unsigned long long t_in = an ? anat_now() : 0;
-  aa.at = t_in;
-#endif
+  AnatWave aw, awr;  // (the workgroup's queue; the lane's re-votes)
+  const Anat an = aw.open(s, round, ANAT_VOTE), ar = awr.open(s, round, ANAT_VOTE);
+  const unsigned long long t_in = an.restart();
   if (s.ctl[CTL_DONE])
     return;
   if (s.ctl[CTL_PALIVE0 + ((round - 1) & 1)] == 0) {  // written by the last fr_update
@@ -417,29 +375,25 @@ template <int R = 8> __global__ void __launch_bounds__(kFB) fr_vote(Dev s, int r
   }
   if (blockIdx.x == 0 && threadIdx.x == 0)
     s.ctl[CTL_PALIVE0 + (round & 1)] = 0;  // this round's fr_update raises it
-#if LMM_ANAT
-  fr_vote_blk<R>(s, round, spb, blockIdx.x, an, &aa, &ar, wc);
-  if (an) {  // the wave's record: queue-count level (lane 0), the re-vote levels of its slowest lane
-    const unsigned long long t_out = anat_now();
+  fr_vote_blk<R>(s, round, spb, blockIdx.x, an, ar);
+  if (an.on()) {  // the wave's record: queue-count level (lane 0), the re-vote levels of its slowest lane
+    const unsigned long long t_out = an.now();
     unsigned lv[5];
 #pragma unroll
     for (int i = 0; i < 5; i++)
-      lv[i] = anat_wmax(ar.lv[i]);
-    const unsigned nre = anat_wmax(wc[1]);
+      lv[i] = anat_wmax(ar.lv(i));
+    const unsigned nre = anat_wmax(an.cnt(1));
     if ((threadIdx.x & (kWave - 1)) == 0) {
-      arec[0] = t_in;
-      arec[1] = t_out;
-      arec[2] = blockIdx.x;
-      arec[3] = aa.lv[0];
+      an.put(0, t_in);
+      an.put(1, t_out);
+      an.put(2, blockIdx.x);
+      an.put(3, an.lv(0));
       for (int i = 0; i < 5; i++)
-        arec[4 + i] = lv[i];
-      arec[9] = nre;
-      arec[10] = wc[0];
+        an.put(4 + i, lv[i]);
+      an.put(9, nre);
+      an.put(10, an.cnt(0));
     }
   }
-#else
-  fr_vote_blk<R>(s, round, spb, blockIdx.x);
-#endif
 }
 
 // Saturation of one 64-element CSC chunk of ready constraint c: saturate_chunk's decisions and arithmetic
@@ -457,30 +411,13 @@ constexpr int kFrSatU = 8;
 // whose other links repeat ~50 times in a chunk — C4 3.63 ms against 3.12: the table's probing and flush cost more;
 // and 16 claimed-row elements per lane per pass instead of 8, a C4 chunk's pushes in one pass — 3.28 against 3.12.)
 
-// (LMM_ANAT: `an` = the chunk's dependent levels into aa->lv: 2 CSC elements + variable states, 3 the claimed rows'
-// elements, 4 their constraints' words, 5 the pushes issued, 6 the claims / values stored; wc[1] chunks, wc[2] fixed
-// variables, wc[3] pushed elements)
+// (an: the chunk's dependent levels: lv[2] CSC elements + variable states, lv[3] the claimed rows' elements, lv[4]
+// their constraints' words, lv[5] the pushes issued, lv[6] the claims / values stored; counters 1 chunks, 2 fixed
+// variables, 3 pushed elements)
 __device__ __forceinline__ void fr_sat_chunk(const Dev& s, int32_t c, double r, uint32_t j0, uint32_t cend,
-                                             int round, int lane, int* pre, bool dup
-#if LMM_ANAT
-                                             , bool an = false, AnatAcc* aa = nullptr, unsigned* wc = nullptr
-#endif
-) {
-#if LMM_ANAT
-  if (an) {
-    aa->at = anat_now();
-    wc[1]++;
-  }
-#define FS_LVL(i, dep)       \
-  do {                       \
-    if (an)                  \
-      ANAT_LVL(*aa, i, dep); \
-  } while (0)
-#else
-#define FS_LVL(i, dep) \
-  do {                 \
-  } while (0)
-#endif
+                                             int round, int lane, int* pre, bool dup, Anat an) {
+  an.restart();
+  an.count(1);
   const int q = lane & 3;
   const uint32_t j = j0 + lane;
   int32_t lv = -1;
@@ -504,12 +441,10 @@ __device__ __forceinline__ void fr_sat_chunk(const Dev& s, int32_t c, double r, 
   } else {
     rb = re = 0;
   }
-#if LMM_ANAT
-  if (an) {
-    ANAT_LVL(*aa, 2, lv);
-    wc[2] += unsigned(__popcll(__ballot(lv >= 0)));
+  if (an.on()) {
+    an.level(2, lv);
+    an.count(2, unsigned(__popcll(__ballot(lv >= 0))));
   }
-#endif
   int incl = len;  // inclusive wave scan of the row lengths
 #pragma unroll
   for (int o = 1; o < kWave; o <<= 1) {
@@ -537,30 +472,26 @@ __device__ __forceinline__ void fr_sat_chunk(const Dev& s, int32_t c, double r, 
       cc[u] = f < total ? s.csr_c[k] : -1;
       ww[u] = f < total ? s.csr_w[k] : 0.0;
     }
-#if LMM_ANAT
-    if (an) {
+    if (an.on()) {
       double sw = 0.0;
 #pragma unroll
       for (int u = 0; u < kFrSatU; u++) {
         sw += ww[u] + double(cc[u]);
-        wc[3] += unsigned(__popcll(__ballot(cc[u] >= 0)));
+        an.count(3, unsigned(__popcll(__ballot(cc[u] >= 0))));
       }
-      ANAT_LVL(*aa, 3, sw);
+      an.level(3, sw);
     }
-#endif
     int32_t cx[kFrSatU];
 #pragma unroll
     for (int u = 0; u < kFrSatU; u++)
       cx[u] = cc[u] >= 0 ? s.cexp[cc[u]] : kCexpDead;  // scales, policy and liveness in one word
-#if LMM_ANAT
-    if (an) {
+    if (an.on()) {
       int32_t sx = 0;
 #pragma unroll
       for (int u = 0; u < kFrSatU; u++)
         sx += cx[u];
-      ANAT_LVL(*aa, 4, sx);
+      an.level(4, sx);
     }
-#endif
 #pragma unroll
     for (int u = 0; u < kFrSatU; u++) {
       const double ox = __shfl(lx, ol[u], kWave);
@@ -592,7 +523,7 @@ __device__ __forceinline__ void fr_sat_chunk(const Dev& s, int32_t c, double r, 
           atomicMax(&s.cst[ec].duse, (unsigned long long)e1);
       }
     }
-    FS_LVL(5, 0u);
+    an.level(5, 0u);
   }
   if (lv >= 0) {  // the claim and the value, last
     if (!dup)
@@ -600,17 +531,10 @@ __device__ __forceinline__ void fr_sat_chunk(const Dev& s, int32_t c, double r, 
     s.x[lv] = lx;
   }
   __builtin_amdgcn_wave_barrier();
-  FS_LVL(6, 0u);
+  an.level(6, 0u);
 }
 
 // The collected ready constraints' chunks, round-robin over the workgroup's waves (sat_flush with fr_sat_chunk).
-#if LMM_ANAT
-#define FR_ANAT_PARAMS , bool an = false, AnatAcc* aa = nullptr, unsigned* wc = nullptr
-#define FR_ANAT_ARGS , an, aa, wc
-#else
-#define FR_ANAT_PARAMS
-#define FR_ANAT_ARGS
-#endif
 // The ready constraints a saturation workgroup collected, with their CSC chunk prefix and — loaded by the ready test
 // itself (round 6) — their CSC range, ratio and duplicate flag, so that a chunk's first loads are its CSC elements.
 template <int NB> struct FrSatLds {
@@ -625,7 +549,7 @@ template <int NB> struct FrSatLds {
 };
 
 template <int NB>
-__device__ __forceinline__ void fr_flush(const Dev& s, int round, FrSatLds<NB>& L FR_ANAT_PARAMS) {
+__device__ __forceinline__ void fr_flush(const Dev& s, int round, FrSatLds<NB>& L, Anat an) {
   constexpr int NBW = NB / kWave;
   const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
   const int ta = L.na, tb = L.nb;
@@ -638,7 +562,7 @@ __device__ __forceinline__ void fr_flush(const Dev& s, int round, FrSatLds<NB>& 
     const int32_t cc = L.rc[k];
     const int ch = g - L.rr[k];
     const double r = L.rt[k];
-    fr_sat_chunk(s, cc, r, L.rb[k] + uint32_t(ch) * kWave, L.re[k], round, lane, L.pre[w], L.rd[k] != 0 FR_ANAT_ARGS);
+    fr_sat_chunk(s, cc, r, L.rb[k] + uint32_t(ch) * kWave, L.re[k], round, lane, L.pre[w], L.rd[k] != 0, an);
     if (ch == 0 && lane == 0)
       s.ctouch[cc] = 2;
   }
@@ -650,8 +574,8 @@ __device__ __forceinline__ void fr_flush(const Dev& s, int round, FrSatLds<NB>& 
 constexpr int kFS = 1024;
 
 template <int NB>
-__device__ __forceinline__ void fr_sat_blk(const Dev& s, int round, int bigch, int vb, FrSatLds<NB>& L
-                                           FR_ANAT_PARAMS) {
+__device__ __forceinline__ void fr_sat_blk(const Dev& s, int round, int bigch, int vb, FrSatLds<NB>& L,
+                                           Anat an) {
   constexpr int NBW = NB / kWave;
   const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
   const int64_t c = int64_t(vb) * NB + threadIdx.x;
@@ -727,49 +651,36 @@ __device__ __forceinline__ void fr_sat_blk(const Dev& s, int round, int bigch, i
       s.ctl[CTL_LASTR] = round;  // plain store: this round fixes variables
   }
   __syncthreads();
-#if LMM_ANAT
-  if (an) {  // the ready test and the workgroup's collection, then the chunks
-    ANAT_LVL(*aa, 0, ta);
-    wc[0] = unsigned(tb);
-  }
-#endif
+  an.level(0, ta);  // the ready test and the workgroup's collection, then the chunks
+  an.count(0, unsigned(tb));
   if (ta)  // workgroup-uniform
-    fr_flush<NB>(s, round, L FR_ANAT_ARGS);
+    fr_flush<NB>(s, round, L, an);
 }
 
 template <int kFS> __global__ void __launch_bounds__(kFS) fr_sat(Dev s, int round, int bigch) {
-#if LMM_ANAT
-  unsigned long long* arec = anat_rec(s, anat_slot(s, round), ANAT_SAT);
-  const bool an = arec != nullptr;
-  AnatAcc aa{};
-  unsigned wc[4] = {0, 0, 0, 0};  // the workgroup's chunks, this wave's chunks, fixed variables, pushed elements
-  const unsigned long long t_in = an ? anat_now() : 0;
-  aa.at = t_in;
-#endif
+  AnatWave aw;  // (counters: the workgroup's chunks, this wave's chunks, fixed variables, pushed elements)
+  const Anat an = aw.open(s, round, ANAT_SAT);
+  const unsigned long long t_in = an.restart();
   if (s.ctl[CTL_DONE])
     return;
   __shared__ FrSatLds<kFS> L;
-#if LMM_ANAT
-  fr_sat_blk<kFS>(s, round, bigch, blockIdx.x, L, an, &aa, wc);
-  if (an && (threadIdx.x & (kWave - 1)) == 0) {
-    arec[0] = t_in;
-    arec[1] = anat_now();
-    arec[2] = blockIdx.x;
+  fr_sat_blk<kFS>(s, round, bigch, blockIdx.x, L, an);
+  if (an.on() && (threadIdx.x & (kWave - 1)) == 0) {
+    an.put(0, t_in);
+    an.put(1, an.now());
+    an.put(2, blockIdx.x);
     for (int i = 0; i < 7; i++)
-      arec[3 + i] = aa.lv[i];
+      an.put(3 + i, an.lv(i));
     for (int i = 0; i < 4; i++)
-      arec[10 + i] = wc[i];
+      an.put(10 + i, an.cnt(i));
   }
-#else
-  fr_sat_blk<kFS>(s, round, bigch, blockIdx.x, L);
-#endif
 }
 
 // The big ready constraints listed by fr_sat (count CTL_NREADY, reset by fr_update): kFrBigWaves waves per
 // constraint over the whole grid, wave k taking chunks k, k + kFrBigWaves, ...
 // (the grid's waves over the list: wave / nwaves; wpre = the calling wave's 64-int LDS scratch)
 __device__ __forceinline__ void fr_sat_big_waves(const Dev& s, int round, int bigw, int nb, int64_t wave,
-                                                 int64_t nwaves, int* wpre FR_ANAT_PARAMS) {
+                                                 int64_t nwaves, int* wpre, Anat an) {
   const int lane = threadIdx.x & (kWave - 1);
   for (int64_t g = wave; g < int64_t(nb) * bigw; g += nwaves) {
     const int32_t c = s.ready[g / bigw];
@@ -778,32 +689,25 @@ __device__ __forceinline__ void fr_sat_big_waves(const Dev& s, int round, int bi
     const uint32_t ce = s.cnst_ptr[c + 1];
     const bool dup = s.cdup[c] != 0;
     for (uint32_t base = s.cnst_ptr[c] + uint32_t(k) * kWave; base < ce; base += uint32_t(bigw) * kWave)
-      fr_sat_chunk(s, c, r, base, ce, round, lane, wpre, dup FR_ANAT_ARGS);
+      fr_sat_chunk(s, c, r, base, ce, round, lane, wpre, dup, an);
     if (k == 0 && lane == 0)
       s.ctouch[c] = 2;
   }
 }
 
 __global__ void __launch_bounds__(kBlock) fr_sat_big(Dev s, int round, int bigw) {
-#if LMM_ANAT
-  unsigned long long* arec = anat_rec(s, anat_slot(s, round), ANAT_SATB);
-  const bool an = arec != nullptr;
-  AnatAcc aa{};
-  unsigned wc[4] = {0, 0, 0, 0};
-  const unsigned long long t_in = an ? anat_now() : 0;
-  aa.at = t_in;
-#endif
+  AnatWave aw;
+  const Anat an = aw.open(s, round, ANAT_SATB);
+  const unsigned long long t_in = an.restart();
   if (s.ctl[CTL_DONE])
     return;
   const int nb = s.ctl[CTL_NREADY];
-#if LMM_ANAT
-  if (an && (threadIdx.x & (kWave - 1)) == 0) {
-    arec[0] = t_in;
-    arec[1] = anat_now();
-    arec[2] = blockIdx.x;
-    arec[10] = unsigned(nb);
+  if (an.on() && (threadIdx.x & (kWave - 1)) == 0) {
+    an.put(0, t_in);
+    an.put(1, an.now());
+    an.put(2, blockIdx.x);
+    an.put(10, unsigned(nb));
   }
-#endif
   if (nb == 0)
     return;
   if (blockIdx.x == 0 && threadIdx.x == 0)
@@ -812,18 +716,14 @@ __global__ void __launch_bounds__(kBlock) fr_sat_big(Dev s, int round, int bigw)
   const int w = threadIdx.x / kWave;
   const int64_t wave = (int64_t(blockIdx.x) * kBlock + threadIdx.x) / kWave;
   const int64_t nwaves = int64_t(gridDim.x) * (kBlock / kWave);
-#if LMM_ANAT
-  fr_sat_big_waves(s, round, bigw, nb, wave, nwaves, wpre[w], an, &aa, wc);
-  if (an && (threadIdx.x & (kWave - 1)) == 0) {
-    arec[1] = anat_now();
+  fr_sat_big_waves(s, round, bigw, nb, wave, nwaves, wpre[w], an);
+  if (an.on() && (threadIdx.x & (kWave - 1)) == 0) {
+    an.put(1, an.now());
     for (int i = 0; i < 7; i++)
-      arec[3 + i] = aa.lv[i];
+      an.put(3 + i, an.lv(i));
     for (int i = 1; i < 4; i++)
-      arec[10 + i] = wc[i];
+      an.put(10 + i, an.cnt(i));
   }
-#else
-  fr_sat_big_waves(s, round, bigw, nb, wave, nwaves, wpre[w]);
-#endif
 }
 
 // Constraint update (maxmin.cpp:603-658; the arithmetic of update_groups) + slot scan.  Workgroup b owns
@@ -843,12 +743,12 @@ struct FrUpdLds {
   uint32_t mf[kFB];
 };
 
-// (LMM_ANAT: `an` = the levels into aa->lv: 0 keys + touch flags, 1 touched records, 2 arithmetic + scan prefix +
-// barrier, 3 slots, 4 queued voters' variable and row, 5 stores + barriers; wc[0] scanned slots)
+// (an: the levels: lv[0] keys + touch flags, lv[1] touched records, lv[2] arithmetic + scan prefix + barrier, lv[3]
+// slots, lv[4] queued voters' variable and row, lv[5] stores + barriers; counter 0 scanned slots)
 // spec (round 6, small systems): a constraint's record, scales, votes, floor and CSC range are loaded with its key and
 // touch flag whether or not it was touched (coalesced, one constraint per lane), one dependent level instead of two.
-__device__ __forceinline__ void fr_update_blk(const Dev& s, int round, double prec, int vb, FrUpdLds& U, bool spec
-                                              FR_ANAT_PARAMS) {
+__device__ __forceinline__ void fr_update_blk(const Dev& s, int round, double prec, int vb, FrUpdLds& U, bool spec,
+                                              Anat an) {
   int& qn = U.qn;
   auto& pre = U.pre;
   uint32_t* mf = U.mf;
@@ -864,10 +764,10 @@ __device__ __forceinline__ void fr_update_blk(const Dev& s, int round, double pr
   const bool in = c < s.nC;
   const uint32_t okey = in ? s.key32[c] : kDead32;
   const unsigned tf = in ? unsigned(s.ctouch[c]) : 0u;  // 1 = received decrements, 2 = saturated this round
-#if LMM_ANAT
-  if (an)
-    ANAT_LVL(*aa, 0, okey + tf);
-#endif
+  // (this level's sum and the next one's stay under on(): computed unconditionally — and then dropped — they changed
+  // how the product build folds the tests below, by a compare and an operand order)
+  if (an.on())
+    an.level(0, okey + tf);
   const bool live0 = okey != kDead32;
   const bool sat = live0 && tf == 2;
   const bool live = live0 && !sat;
@@ -891,10 +791,8 @@ __device__ __forceinline__ void fr_update_blk(const Dev& s, int round, double pr
     cb = s.cnst_ptr[c];
     cend = s.cnst_ptr[c + 1];
   }
-#if LMM_ANAT
-  if (an)
-    ANAT_LVL(*aa, 1, rem + use + bnd + double(qx + qy + qz) + double(ce + nv + int(mfl + cb + cend)));
-#endif
+  if (an.on())
+    an.level(1, rem + use + bnd + double(qx + qy + qz) + double(ce + nv + int(mfl + cb + cend)));
   const bool fat = tch && (ce & kCexpFat);
   // FATPIPE: recompute only when a removed element reached the usage (fat_bits in duse)
   const bool fre = fat && !(__longlong_as_double((long long)qy) < use);
@@ -965,12 +863,8 @@ __device__ __forceinline__ void fr_update_blk(const Dev& s, int round, double pr
   pre[w][lane] = incl - len;
   mf[threadIdx.x] = kNoVoter;
   __syncthreads();  // (qn, pre, mf)
-#if LMM_ANAT
-  if (an) {
-    ANAT_LVL(*aa, 2, total);
-    wc[0] = unsigned(total);
-  }
-#endif
+  an.level(2, total);
+  an.count(0, unsigned(total));
   const uint32_t seg = s.cnst_ptr[int64_t(vb) * kFB];
   for (int f0 = 0; f0 < total; f0 += kFrScanU * kWave) {  // wave-uniform (one pass up to 512 slots)
     int ol[kFrScanU];
@@ -988,15 +882,13 @@ __device__ __forceinline__ void fr_update_blk(const Dev& s, int round, double pr
       jj[u] = uint32_t(__shfl(int(cb), o, kWave)) + uint32_t(f - pre[w][o]);
       fl[u] = f < total ? s.vslot[jj[u]] : kNoVoter;
     }
-#if LMM_ANAT
-    if (an) {
+    if (an.on()) {
       uint32_t sf = 0;
 #pragma unroll
       for (int u = 0; u < kFrScanU; u++)
         sf += fl[u];
-      ANAT_LVL(*aa, 3, sf);
+      an.level(3, sf);
     }
-#endif
     bool q[kFrScanU];
     int32_t qv[kFrScanU];
     unsigned long long qr[kFrScanU];
@@ -1009,15 +901,13 @@ __device__ __forceinline__ void fr_update_blk(const Dev& s, int round, double pr
       qv[u] = q[u] ? s.csc_v[jj[u]] : 0;
       qr[u] = q[u] ? s.csc_row[jj[u]] : 0ull;
     }
-#if LMM_ANAT
-    if (an) {
+    if (an.on()) {
       unsigned long long sq = 0;
 #pragma unroll
       for (int u = 0; u < kFrScanU; u++)
         sq += qr[u] + unsigned(qv[u]);
-      ANAT_LVL(*aa, 4, sq);
+      an.level(4, sq);
     }
-#endif
 #pragma unroll
     for (int u = 0; u < kFrScanU; u++) {
       const unsigned long long m = __ballot(q[u]);
@@ -1067,37 +957,25 @@ __device__ __forceinline__ void fr_update_blk(const Dev& s, int round, double pr
   }
   if (__syncthreads_or(tch || sat) && threadIdx.x == 0)
     s.ctl[CTL_LASTR] = round;  // plain store: the last round that changed a constraint
-#if LMM_ANAT
-  if (an)
-    ANAT_LVL(*aa, 5, 0u);
-#endif
+  an.level(5, 0u);
 }
 
 __global__ void __launch_bounds__(kFB) fr_update(Dev s, int round, double prec, int spec) {
-#if LMM_ANAT
-  unsigned long long* arec = anat_rec(s, anat_slot(s, round), ANAT_UPD);
-  const bool an = arec != nullptr;
-  AnatAcc aa{};
-  unsigned wc[1] = {0};
-  const unsigned long long t_in = an ? anat_now() : 0;
-  aa.at = t_in;
-#endif
+  AnatWave aw;
+  const Anat an = aw.open(s, round, ANAT_UPD);
+  const unsigned long long t_in = an.restart();
   if (s.ctl[CTL_DONE])
     return;
   __shared__ FrUpdLds U;
-#if LMM_ANAT
-  fr_update_blk(s, round, prec, blockIdx.x, U, spec != 0, an, &aa, wc);
-  if (an && (threadIdx.x & (kWave - 1)) == 0) {
-    arec[0] = t_in;
-    arec[1] = anat_now();
-    arec[2] = blockIdx.x;
+  fr_update_blk(s, round, prec, blockIdx.x, U, spec != 0, an);
+  if (an.on() && (threadIdx.x & (kWave - 1)) == 0) {
+    an.put(0, t_in);
+    an.put(1, an.now());
+    an.put(2, blockIdx.x);
     for (int i = 0; i < 6; i++)
-      arec[3 + i] = aa.lv[i];
-    arec[9] = wc[0];
+      an.put(3 + i, an.lv(i));
+    an.put(9, an.cnt(0));
   }
-#else
-  fr_update_blk(s, round, prec, blockIdx.x, U, spec != 0);
-#endif
 }
 
 }  // namespace lmmdev

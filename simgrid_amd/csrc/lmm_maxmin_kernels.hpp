@@ -439,31 +439,15 @@ constexpr int kFilt = LMM_KFILT;  // rows per lane per filter step (their loads 
 // rows loop over the rest.  Every load indexed by the row or its variable is issued at once.
 // kRec: the row's variable and CSR range from the packed records (crec; the multi-launch engine's short-row
 // vote only — other instantiations, e.g. the persistent kernel, keep their register budget).
-// (LMM_ANAT: `an` = record the dependent levels into aa.lv[0..5]: row record, variable state, row elements, keys,
-// exact ratios, the vote's stores and atomics)
-#if LMM_ANAT
-#define VR_ANAT_PARAMS , bool an = false, AnatAcc* aa = nullptr
-#define VR_LVL(i, dep)       \
-  do {                       \
-    if (an)                  \
-      ANAT_LVL(*aa, i, dep); \
-  } while (0)
-#else
-#define VR_ANAT_PARAMS
-#define VR_LVL(i, dep) \
-  do {                 \
-  } while (0)
-#endif
+// (an: the dependent levels into lv[0..5]: row record, variable state, row elements, keys, exact ratios, the vote's
+// stores and atomics)
 // kRdq: a constraint this re-vote made ready (nothing votes elsewhere any more) is returned in *rdq_c for the
 // caller's workgroup-wide queueing (rdq_push_lds), or queued here when rdq_c is null.
 template <int R, bool kRec = false, bool kRdq = false>
 __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64_t row, int* st_rows,
-                                         int* st_elems, const uint16_t* __restrict__ key, int* rdq_c = nullptr
-                                         VR_ANAT_PARAMS) {
-#if LMM_ANAT
-  if (an)
-    aa->at = anat_now();
-#endif
+                                         int* st_elems, const uint16_t* __restrict__ key, int* rdq_c = nullptr,
+                                         Anat an = Anat()) {
+  an.restart();
   const int32_t* __restrict__ cvar = s.cvar[buf];
   const uint32_t* __restrict__ crow = s.crow[buf];
   const int32_t* __restrict__ ccol = s.ccol[buf];
@@ -483,13 +467,13 @@ __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64
     b = crow[row];
     e = crow[row + 1];
   }
-  VR_LVL(0, b + e + uint32_t(t) + uint32_t(cv));
+  an.level(0, b + e + uint32_t(t) + uint32_t(cv));
   const int v = rvar(cv);
   const int32_t vst = s.vstate[v];
   const bool bnd = rbounded(cv);
   const double vb = bnd ? s.vbound[v] : -1.0;
   const double p = bnd ? s.pen[v] : 1.0;  // read below only when vb > 0
-  VR_LVL(1, vst);
+  an.level(1, vst);
   // (the row's gathers wait for the variable's state: a fixed variable's row — every variable once, when
   // its saturated target dies — retires without them; measured cheaper on C2 than issuing them early)
   if (vst != 0) {  // fixed by a saturation since: retire the row
@@ -505,15 +489,13 @@ __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64
 #pragma unroll
   for (int i = 0; i < R; i++)
     cc[i] = b + i < e ? ccol[b + i] : -1;
-#if LMM_ANAT
-  {
+  if (an.on()) {
     int32_t ccs = 0;
 #pragma unroll
     for (int i = 0; i < R; i++)
       ccs += cc[i];
-    VR_LVL(2, ccs);
+    an.level(2, ccs);
   }
-#endif
 #pragma unroll
   for (int i = 0; i < R; i++)
     kk[i] = cc[i] >= 0 ? key[cc[i]] : kDeadKey;
@@ -528,7 +510,7 @@ __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64
 #pragma unroll 4
   for (uint32_t j = b + R; j < e; j++)
     mk = min(mk, (unsigned)key[ccol[j]]);
-  VR_LVL(3, mk + kt);
+  an.level(3, mk + kt);
   if (mk == kDeadKey) {  // every constraint of v left the light table: v stays at 0
     s.vstate[v] = round + 1;  // fixed / dropped in this round
     rtgt[row] = kRetired;
@@ -584,7 +566,7 @@ __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64
       }
     }
   }
-  VR_LVL(4, minr + double(newt));
+  an.level(4, minr + double(newt));
   if (vb > 0 && vb * p < minr) {  // fixed at its bound (maxmin.cpp:587-589)
     s.vstate[v] = round + 1;  // fixed / dropped in this round
     s.x[v] = vb;
@@ -624,7 +606,7 @@ __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64
       else
         rdq_push(s, newt, round);
     }
-    VR_LVL(5, old);
+    an.level(5, old);
   } else {
     atomicSub(&s.nvote[newt], mult_new);
   }
@@ -654,20 +636,13 @@ __device__ __forceinline__ void vote_wave_range(int64_t lo, int64_t hi, int64_t&
   whi = wlo + gpw * kWave < hi ? wlo + gpw * kWave : hi;
 }
 
-// kPre: the targets and floors of the wave's first filter step were loaded by the caller (tt0 / sk0, issued before
-// the bitmap copy, so that their latency overlaps it).
-// LMM_ANAT: `an` = stamp the filter steps and re-vote batches of this wave into aa (lv[6] filter loads, lv[7] filter
-// gathers, lv[8] re-vote batches; w[0] steps, w[1] batches) and vote_row's levels into ar.
-#if LMM_ANAT
-#define VW_ANAT_PARAMS , bool an = false, AnatAcc* aa = nullptr, AnatAcc* ar = nullptr, unsigned* wcnt = nullptr
-#else
-#define VW_ANAT_PARAMS
-#endif
-template <bool kBits, int R, int F, int kDiag, bool kRec = false, bool kRdq = false, bool kPre = false>
+// an: the filter steps and re-vote batches of this wave (lv[6] filter loads, lv[7] filter gathers, lv[8] re-vote
+// batches; counters 0 steps, 1 batches); ar: vote_row's levels.
+template <bool kBits, int R, int F, int kDiag, bool kRec = false, bool kRdq = false>
 __device__ __forceinline__ int vote_waves(const Dev& s, int buf, int round, int64_t lo, int64_t hi,
                                           const uint64_t* bits, int* qw, int* st_rows, int* st_elems,
-                                          const uint16_t* __restrict__ key, const int* tt0 = nullptr,
-                                          const unsigned* sk0 = nullptr, RdqLds* rql = nullptr VW_ANAT_PARAMS) {
+                                          const uint16_t* __restrict__ key, RdqLds* rql = nullptr, Anat an = Anat(),
+                                          Anat ar = Anat()) {
   const int lane = threadIdx.x & (kWave - 1);
   int64_t wlo, whi;
   vote_wave_range(lo, hi, wlo, whi);
@@ -680,35 +655,21 @@ __device__ __forceinline__ int vote_waves(const Dev& s, int buf, int round, int6
   for (int64_t base = wlo; base < whi; base += int64_t(F) * kWave) {  // wave-uniform
     int tt[F];
     unsigned sk[F];
-#if LMM_ANAT
-    if (an) {
-      aa->at = anat_now();
-      wcnt[0]++;
-    }
-#endif
-    if (kPre && base == wlo) {  // wave-uniform
+    an.restart();
+    an.count(0);
 #pragma unroll
-      for (int u = 0; u < F; u++) {
-        tt[u] = tt0[u];
-        sk[u] = sk0[u];
-      }
-    } else {
-#pragma unroll
-      for (int u = 0; u < F; u++) {
-        const int64_t row = base + u * kWave + lane;
-        tt[u] = row < whi ? rtgt[row] : kRetired;
-        sk[u] = row < whi ? unsigned(skey[row]) : 1u;
-      }
+    for (int u = 0; u < F; u++) {
+      const int64_t row = base + u * kWave + lane;
+      tt[u] = row < whi ? rtgt[row] : kRetired;
+      sk[u] = row < whi ? unsigned(skey[row]) : 1u;
     }
-#if LMM_ANAT
-    if (an) {
+    if (an.on()) {
       int ts = 0;
 #pragma unroll
       for (int u = 0; u < F; u++)
         ts += tt[u] + int(sk[u]);
-      ANAT_LVL(*aa, 6, ts);
+      an.level(6, ts);
     }
-#endif
     bool ch[F];
 #pragma unroll
     for (int u = 0; u < F; u++) {
@@ -723,15 +684,13 @@ __device__ __forceinline__ int vote_waves(const Dev& s, int buf, int round, int6
       kt[u] = ch[u] ? key[tt[u]] : 0u;
       cg[u] = (kBits && !ch[u] && tt[u] >= 0 && sk[u] == 0) ? unsigned(s.chg[tt[u]]) : 0x10000u;
     }
-#if LMM_ANAT
-    if (an) {
+    if (an.on()) {
       unsigned ks = 0;
 #pragma unroll
       for (int u = 0; u < F; u++)
         ks += kt[u] + cg[u];
-      ANAT_LVL(*aa, 7, ks);
+      an.level(7, ks);
     }
-#endif
     unsigned needm = 0;
 #pragma unroll
     for (int u = 0; u < F; u++) {
@@ -765,47 +724,28 @@ __device__ __forceinline__ int vote_waves(const Dev& s, int buf, int round, int6
         const int row = qw[qn + lane];
         __builtin_amdgcn_wave_barrier();
         int pc = -1;  // (kRdq) a constraint this lane's re-vote made ready
-#if LMM_ANAT
-        if (an) {
-          aa->at = anat_now();
-          wcnt[1]++;
-        }
+        an.restart();
+        an.count(1);
         if (kDiag == 0)
-          vote_row<R, kRec, kRdq>(s, buf, round, row, st_rows, st_elems, key, &pc, an, ar);
+          vote_row<R, kRec, kRdq>(s, buf, round, row, st_rows, st_elems, key, &pc, ar);
         if (kRdq && kDiag == 0)
           rdq_push_lds(s, pc, round, rql);
-        if (an)
-          ANAT_LVL(*aa, 8, 0u);
-#else
-        if (kDiag == 0)
-          vote_row<R, kRec, kRdq>(s, buf, round, row, st_rows, st_elems, key, &pc);
-        if (kRdq && kDiag == 0)
-          rdq_push_lds(s, pc, round, rql);
-#endif
+        an.level(8, 0u);
       }
     }
   }
   __builtin_amdgcn_wave_barrier();
-#if LMM_ANAT
-  if (an && qn > 0) {
-    aa->at = anat_now();
-    wcnt[1]++;
+  if (an.on() && qn > 0) {
+    an.restart();
+    an.count(1);
   }
   int pc = -1;
   if (kDiag == 0 && lane < qn)
-    vote_row<R, kRec, kRdq>(s, buf, round, qw[lane], st_rows, st_elems, key, &pc, an, ar);
-  __builtin_amdgcn_wave_barrier();
+    vote_row<R, kRec, kRdq>(s, buf, round, qw[lane], st_rows, st_elems, key, &pc, ar);
   if (kRdq && kDiag == 0)
     rdq_push_lds(s, pc, round, rql);
-  if (an && qn > 0)
-    ANAT_LVL(*aa, 8, 0u);
-#else
-  int pc = -1;
-  if (kDiag == 0 && lane < qn)
-    vote_row<R, kRec, kRdq>(s, buf, round, qw[lane], st_rows, st_elems, key, &pc);
-  if (kRdq && kDiag == 0)
-    rdq_push_lds(s, pc, round, rql);
-#endif
+  if (an.on() && qn > 0)
+    an.level(8, 0u);
   if (kDiag == 1 && s.vstat && round < kStatRounds) {
     int32_t* d = s.vstat + 2 * (int64_t(round) * kMaxBlocks + kDiagSlot);
     for (int k = 0; k < 4; k++) {
@@ -883,20 +823,14 @@ __global__ void __launch_bounds__(kBlock) mm_vote_diagcount(Dev s, int round) {
 // Multi-launch engine, short rows (mean length <= 8): one 1024-thread workgroup per CU (the bitmap takes up
 // to kBitWords * 8 B of LDS), one contiguous chunk of rows per workgroup.
 constexpr int kVBlock = 1024;
-// LMM_VOTE_PRE: the first filter step's loads issued before the bitmap copy (build knob, measurement).  Round 5, same
-// box: 24.313 / 24.390 ms against 24.340 / 24.309 without (neutral: the copy is not the vote's critical path); off.
-#ifndef LMM_VOTE_PRE
-#define LMM_VOTE_PRE 0
-#endif
+// (Round 5 measured the first filter step's loads issued before the bitmap copy: 24.313 / 24.390 ms against 24.340 /
+// 24.309 without, profiles/r05_ab_c2_spec2.json — neutral, the copy is not the vote's critical path; removed.)
 template <int B, bool kBits, int kDiag = 0, bool kRec = false, bool kRdq = false>
 __global__ void __launch_bounds__(B) mm_vote_lane(Dev s, int round) {
-#if LMM_ANAT
-  unsigned long long* arec = kDiag == 0 ? anat_rec(s, anat_slot(s, round), ANAT_VOTE) : nullptr;
-  const bool an = arec != nullptr;
-  AnatAcc aa{}, ar{};
-  unsigned wcnt[2] = {0, 0};
-  const unsigned long long t_in = an ? anat_now() : 0;
-#endif
+  AnatWave aw, awr;  // (the wave's filter steps and batches; vote_row's levels)
+  const Anat an = kDiag == 0 ? aw.open(s, round, ANAT_VOTE) : Anat();
+  const Anat ar = kDiag == 0 ? awr.open(s, round, ANAT_VOTE) : Anat();
+  const unsigned long long t_in = an.now();
   if (s.ctl[CTL_DONE])
     return;
   const int buf = s.ctl[CTL_BUF];
@@ -912,25 +846,10 @@ __global__ void __launch_bounds__(B) mm_vote_lane(Dev s, int round) {
   const int64_t per = ((nrows + gridDim.x - 1) / gridDim.x + kWave - 1) / kWave * kWave;  // rows per workgroup
   const int64_t lo = int64_t(blockIdx.x) * per;
   const int64_t hi = lo + per < nrows ? lo + per : nrows;
-  constexpr bool kPre = LMM_VOTE_PRE != 0 && kBits && kDiag == 0;
-  int tt0[kPre ? kFilt : 1];
-  unsigned sk0[kPre ? kFilt : 1];
-  if (kPre) {  // the wave's first filter step, in flight during the bitmap copy
-    int64_t wlo, whi;
-    vote_wave_range(lo, hi, wlo, whi);
-#pragma unroll
-    for (int u = 0; u < (kPre ? kFilt : 1); u++) {
-      const int64_t row = wlo + u * kWave + (threadIdx.x & (kWave - 1));
-      tt0[u] = row < whi ? s.rtgt[buf][row] : kRetired;
-      sk0[u] = row < whi ? unsigned(s.skey[buf][row]) : 1u;
-    }
-  }
   if (kBits)
     load_bits<B, LMM_BITS_STAGGER != 0, LMM_BITS_UNROLL>(s, bits);
   __syncthreads();
-#if LMM_ANAT
-  const unsigned long long t_bits = an ? anat_now() : 0;
-#endif
+  const unsigned long long t_bits = an.now();
   if (kDiag == 2) {  // measurement only: the bitmap load alone, and the changed-constraint count
     if (kBits && blockIdx.x == 0 && s.vstat && round < kStatRounds) {
       int pc = 0;
@@ -942,46 +861,37 @@ __global__ void __launch_bounds__(B) mm_vote_lane(Dev s, int round) {
       s.ctl[CTL_WORDS - 1] = 1;
     return;
   }
-#if LMM_ANAT
   int nq = 0;
   if (lo < hi)
-    nq = vote_waves<kBits, 8, kFilt, kDiag, kRec, kRdq, kPre>(s, buf, round, lo, hi, bits,
-                                                              q + (threadIdx.x / kWave) * kQW, &st_rows, &st_elems,
-                                                              s.key, tt0, sk0, &rql, an, &aa, &ar, wcnt);
+    nq = vote_waves<kBits, 8, kFilt, kDiag, kRec, kRdq>(s, buf, round, lo, hi, bits, q + (threadIdx.x / kWave) * kQW,
+                                                        &st_rows, &st_elems, s.key, &rql, an, ar);
   if (kRdq && kDiag == 0)
     rdq_flush_lds(s, round, &rql);
-  if (an) {  // the wave's record (vote_row's levels: the slowest lane of the wave)
-    const unsigned long long t_out = anat_now();
+  if (an.on()) {  // the wave's record (vote_row's levels: the slowest lane of the wave)
+    const unsigned long long t_out = an.now();
     unsigned lv[6];
 #pragma unroll
     for (int i = 0; i < 6; i++)
-      lv[i] = anat_wmax(ar.lv[i]);
+      lv[i] = anat_wmax(ar.lv(i));
     int64_t wlo, whi;
     vote_wave_range(lo, hi, wlo, whi);
     if ((threadIdx.x & (kWave - 1)) == 0) {
-      arec[0] = t_in;
-      arec[1] = t_out;
-      arec[2] = blockIdx.x;
-      arec[3] = t_bits;
-      arec[4] = wcnt[0];
-      arec[5] = aa.lv[6];
-      arec[6] = aa.lv[7];
-      arec[7] = wcnt[1];
-      arec[8] = aa.lv[8];
+      an.put(0, t_in);
+      an.put(1, t_out);
+      an.put(2, blockIdx.x);
+      an.put(3, t_bits);
+      an.put(4, an.cnt(0));
+      an.put(5, an.lv(6));
+      an.put(6, an.lv(7));
+      an.put(7, an.cnt(1));
+      an.put(8, an.lv(8));
 #pragma unroll
       for (int i = 0; i < 6; i++)
-        arec[9 + i] = lv[i];
-      arec[15] = unsigned(nq);
-      arec[16] = whi > wlo ? unsigned(whi - wlo) : 0u;
+        an.put(9 + i, lv[i]);
+      an.put(15, unsigned(nq));
+      an.put(16, whi > wlo ? unsigned(whi - wlo) : 0u);
     }
   }
-#else
-  if (lo < hi)
-    vote_waves<kBits, 8, kFilt, kDiag, kRec, kRdq, kPre>(s, buf, round, lo, hi, bits, q + (threadIdx.x / kWave) * kQW,
-                                                         &st_rows, &st_elems, s.key, tt0, sk0, &rql);
-  if (kRdq && kDiag == 0)
-    rdq_flush_lds(s, round, &rql);
-#endif
   if (s.vstat && kDiag == 0) {
     __syncthreads();
     if (threadIdx.x == 0 && round < kStatRounds && blockIdx.x < kMaxBlocks) {
@@ -1037,32 +947,13 @@ __global__ void __launch_bounds__(kBlock) mm_ready(Dev s) {
 #endif
 constexpr int kSatU = LMM_KSATU;
 
-// (LMM_ANAT: `an` = stamp the chunk's dependent levels into aa: lv[1] CSC element loads, lv[2] variable states and
-// claims, lv[3] the claimed rows' elements, lv[4] their constraints' words, lv[5] the pushes; wc[1] chunks, wc[2]
-// fixed variables, wc[3] pushed elements)
-#if LMM_ANAT
-#define SC_ANAT_PARAMS , bool an = false, AnatAcc* aa = nullptr, unsigned* wc = nullptr
-#define SC_ANAT_ARGS , an, aa, wc
-#define SC_LVL(i, dep)       \
-  do {                       \
-    if (an)                  \
-      ANAT_LVL(*aa, i, dep); \
-  } while (0)
-#else
-#define SC_ANAT_PARAMS
-#define SC_ANAT_ARGS
-#define SC_LVL(i, dep) \
-  do {                 \
-  } while (0)
-#endif
+// (an: the chunk's dependent levels: lv[1] CSC element loads, lv[2] variable states and claims, lv[3] the claimed
+// rows' elements, lv[4] their constraints' words, lv[5] the pushes; counters 1 chunks, 2 fixed variables, 3 pushed
+// elements)
 __device__ __forceinline__ void saturate_chunk(const Dev& s, int32_t c, double r, uint32_t j0, uint32_t ce,
-                                               int round, int lane, int* pre, bool dup SC_ANAT_PARAMS) {
-#if LMM_ANAT
-  if (an) {
-    aa->at = anat_now();
-    wc[1]++;
-  }
-#endif
+                                               int round, int lane, int* pre, bool dup, Anat an = Anat()) {
+  an.restart();
+  an.count(1);
   const int q = lane & 3;
   const uint32_t j = j0 + lane;
   int32_t lv = -1;
@@ -1077,7 +968,7 @@ __device__ __forceinline__ void saturate_chunk(const Dev& s, int32_t c, double r
     rb = uint32_t(row);
     re = uint32_t(row >> 32);
   }
-  SC_LVL(1, uint32_t(lv) + rb + re);
+  an.level(1, uint32_t(lv) + rb + re);
   if (j < ce) {
     if (s.vstate[lv] != 0)
       lv = -1;
@@ -1094,12 +985,10 @@ __device__ __forceinline__ void saturate_chunk(const Dev& s, int32_t c, double r
   } else {
     rb = re = 0;
   }
-#if LMM_ANAT
-  if (an) {
-    ANAT_LVL(*aa, 2, lv);
-    wc[2] += unsigned(__popcll(__ballot(lv >= 0)));
+  if (an.on()) {
+    an.level(2, lv);
+    an.count(2, unsigned(__popcll(__ballot(lv >= 0))));
   }
-#endif
   int incl = len;  // inclusive wave scan of the row lengths
 #pragma unroll
   for (int o = 1; o < kWave; o <<= 1) {
@@ -1128,15 +1017,13 @@ __device__ __forceinline__ void saturate_chunk(const Dev& s, int32_t c, double r
       cc[u] = f < total ? s.csr_c[kk[u]] : -1;
       ww[u] = f < total ? s.csr_w[kk[u]] : 0.0;  // with the constraint id: one round trip
     }
-#if LMM_ANAT
-    if (an) {
+    if (an.on()) {
       double sw = 0.0;
 #pragma unroll
       for (int u = 0; u < kSatU; u++)
         sw += ww[u] + double(cc[u]);
-      ANAT_LVL(*aa, 3, sw);
+      an.level(3, sw);
     }
-#endif
     long long a0[kSatU], a1[kSatU];  // fixed-point decrements (CstRec)
     bool fat[kSatU];
 #pragma unroll
@@ -1156,17 +1043,15 @@ __device__ __forceinline__ void saturate_chunk(const Dev& s, int32_t c, double r
         a1[u] = fat[u] ? (long long)fat_bits(w / op) : (long long)dec_q(w / op, cexp_use(ce));
       }
     }
-#if LMM_ANAT
-    if (an) {
+    if (an.on()) {
       long long sa = 0;
 #pragma unroll
       for (int u = 0; u < kSatU; u++) {
         sa += a0[u] + a1[u];
-        wc[3] += unsigned(__popcll(__ballot(cc[u] >= 0)));
+        an.count(3, unsigned(__popcll(__ballot(cc[u] >= 0))));
       }
-      ANAT_LVL(*aa, 4, sa);
+      an.level(4, sa);
     }
-#endif
 #pragma unroll
     for (int u = 0; u < kSatU; u++) {
       const int nel = total - f0 - u * kWave;
@@ -1185,7 +1070,7 @@ __device__ __forceinline__ void saturate_chunk(const Dev& s, int32_t c, double r
           atomicMax(&s.cst[ec].duse, (unsigned long long)e1);
       }
     }
-    SC_LVL(5, 0u);
+    an.level(5, 0u);
   }
   __builtin_amdgcn_wave_barrier();
 }
@@ -1306,9 +1191,9 @@ template <int K> __device__ __forceinline__ void saturate_one(const Dev& s, int3
 // (the same with the constraint's ratio, CSC range and duplicate flag already loaded)
 template <int K> __device__ __forceinline__ void saturate_one_pre(const Dev& s, int32_t c, int k, int round, int lane,
                                                                   int* pre, double r, uint32_t cb, uint32_t ce,
-                                                                  bool dup SC_ANAT_PARAMS) {
+                                                                  bool dup, Anat an) {
   for (uint32_t base = cb + uint32_t(k) * kWave; base < ce; base += K * kWave)  // wave-uniform
-    saturate_chunk(s, c, r, base, ce, round, lane, pre, dup SC_ANAT_ARGS);
+    saturate_chunk(s, c, r, base, ce, round, lane, pre, dup, an);
   if (k == 0 && lane == 0)
     s.ctouch[c] = 2;
 }
@@ -1378,22 +1263,14 @@ template <int K> __global__ void __launch_bounds__(kBlock) mm_saturate(Dev s, in
 // an entry is saturated when it is still alive with nothing voting elsewhere (every vote of the round is in).
 // Block 0 empties the other parity's vote queue, which the next round's vote fills.
 // A candidate's ratio, CSC range and duplicate flag are loaded with its key and vote count (round 5, same box, two
-// passes, profiles/r05_ab_c2_spec2.json: C2 24.285-24.293 ms against 24.309-24.340 without).  LMM_SATQ_PIPE (build
-// knob): the next task's candidate state loaded ahead (round 6).  Also measured in round 6 and removed: a batched form
-// (a wave's 64 tasks' states in one load, the ready tasks' first chunks 2 / 4 at a time, the claimed variables gathered
-// in LDS and pushed 64 at a time; with 64- or 32-element chunks): 23.54-23.68 ms against 23.53 on the same box.
-#ifndef LMM_SATQ_PIPE
-#define LMM_SATQ_PIPE 1
-#endif
+// passes, profiles/r05_ab_c2_spec2.json: C2 24.285-24.293 ms against 24.309-24.340 without).  Also measured in round 6
+// and removed: a batched form (a wave's 64 tasks' states in one load, the ready tasks' first chunks 2 / 4 at a time, the
+// claimed variables gathered in LDS and pushed 64 at a time; with 64- or 32-element chunks): 23.54-23.68 ms against
+// 23.53 on the same box.
 template <int K> __global__ void __launch_bounds__(kBlock) mm_saturate_q(Dev s, int round, int ublocks) {
-#if LMM_ANAT
-  unsigned long long* arec = anat_rec(s, anat_slot(s, round), ANAT_SAT);
-  const bool an = arec != nullptr;
-  AnatAcc aa_s{};
-  AnatAcc* aa = &aa_s;
-  unsigned wc[4] = {0, 0, 0, 0};  // candidates, chunks, fixed variables, pushed elements
-  const unsigned long long t_in = an ? anat_now() : 0;
-#endif
+  AnatWave aw;  // (counters: candidates, chunks, fixed variables, pushed elements)
+  const Anat an = aw.open(s, round, ANAT_SAT);
+  const unsigned long long t_in = an.now();
   if (s.ctl[CTL_DONE])
     return;
   if (blockIdx.x == 0 && threadIdx.x == 0)
@@ -1433,9 +1310,7 @@ template <int K> __global__ void __launch_bounds__(kBlock) mm_saturate_q(Dev s, 
     acc += loc[k];
   }
   __syncthreads();
-#if LMM_ANAT
-  const unsigned long long t_pre = an ? anat_now() : 0;
-#endif
+  const unsigned long long t_pre = an.now();
   const int nq = s.ctl[CTL_RDQ0 + (round & 1)];
   const int32_t* __restrict__ q = s.rdq[round & 1];
   const int64_t wave = (int64_t(blockIdx.x) * kBlock + threadIdx.x) / kWave;
@@ -1452,11 +1327,11 @@ template <int K> __global__ void __launch_bounds__(kBlock) mm_saturate_q(Dev s, 
         lo += step;
     return s.useg[int64_t(lo) * kUSeg + (i - pre[lo])];
   };
-#if LMM_SATQ_PIPE
   // Software-pipelined over the wave's tasks (round 6): the next task's candidate state (key, vote count, ratio, CSC
   // range, duplicate flag) and the candidate id of the task after it are loaded before this task's chunks, so a task
   // starts with its CSC element loads instead of two dependent levels (candidate id, then its state).  The round
   // anatomy (profiles/r06_c2_round_anatomy.json) shows a tail-round wave running ~9 tasks one after the other.
+  // (Round-6 A/B, profiles/r06_ab.json: C2 23.62-23.63 ms against 23.74-23.80 with the plain loop, which is gone.)
   struct CandSt {
     int32_t c;
     unsigned kc;
@@ -1488,56 +1363,26 @@ template <int K> __global__ void __launch_bounds__(kBlock) mm_saturate_q(Dev s, 
   int32_t cnext = wave + nwaves < T ? cand_of(wave + nwaves) : -1;
   for (int64_t g = wave; g < T; g += nwaves) {  // wave-uniform
     const int k = int(g % K);
-#if LMM_ANAT
-    if (an) {
-      aa->at = anat_now();
-      wc[0]++;
-    }
-#endif
-    SC_LVL(6, cur.r + double(cur.kc + unsigned(cur.nv) + cur.cb + cur.ce + unsigned(cur.dup)));
+    an.restart();
+    an.count(0);
+    an.level(6, cur.r + double(cur.kc + unsigned(cur.nv) + cur.cb + cur.ce + unsigned(cur.dup)));
     const CandSt nxt = state_of(cnext);  // (issued before this task's chunk loads)
     cnext = g + 2 * nwaves < T ? cand_of(g + 2 * nwaves) : -1;
     if (cur.kc != kDeadKey && cur.nv == 0) {  // (the round's CTL_LASTR: mm_update, from the constraints saturated here)
-      saturate_one_pre<K>(s, cur.c, k, round, lane, wpre[w], cur.r, cur.cb, cur.ce, cur.dup SC_ANAT_ARGS);
+      saturate_one_pre<K>(s, cur.c, k, round, lane, wpre[w], cur.r, cur.cb, cur.ce, cur.dup, an);
     }
     cur = nxt;
   }
-#else
-  for (int64_t g = wave; g < T; g += nwaves) {  // wave-uniform
-    const int k = int(g % K);
-#if LMM_ANAT
-    if (an) {
-      aa->at = anat_now();
-      wc[0]++;
-    }
-#endif
-    const int32_t c = cand_of(g);
-    SC_LVL(0, c);
-    // the constraint's ratio, CSC range and duplicate flag loaded with its key and count (one dependent level less;
-    // a candidate that is not ready discards them)
-    const unsigned kc = s.key[c];
-    const int nv = s.nvote[c];
-    const double r = ld_rlx(&s.cst[c].ratio);
-    const uint32_t cb = s.cnst_ptr[c], cend = s.cnst_ptr[c + 1];
-    const bool dup = s.cdup[c] != 0;
-    SC_LVL(6, r + double(kc + unsigned(nv) + cb + cend + unsigned(dup)));
-    if (kc == kDeadKey || nv != 0)
-      continue;
-    saturate_one_pre<K>(s, c, k, round, lane, wpre[w], r, cb, cend, dup SC_ANAT_ARGS);
-  }
-#endif
-#if LMM_ANAT
-  if (an && lane == 0) {
-    arec[0] = t_in;
-    arec[1] = anat_now();
-    arec[2] = blockIdx.x;
-    arec[3] = t_pre;
+  if (an.on() && lane == 0) {
+    an.put(0, t_in);
+    an.put(1, an.now());
+    an.put(2, blockIdx.x);
+    an.put(3, t_pre);
     for (int f = 0; f < 7; f++)
-      arec[4 + f] = aa->lv[f];
+      an.put(4 + f, an.lv(f));
     for (int f = 0; f < 4; f++)
-      arec[11 + f] = wc[f];
+      an.put(11 + f, an.cnt(f));
   }
-#endif
 }
 
 // Round phase 4 — constraint update: maxmin.cpp:603-658, one wave = 64 consecutive constraints (identity
@@ -1550,22 +1395,15 @@ template <int K> __global__ void __launch_bounds__(kBlock) mm_saturate_q(Dev s, 
 // K groups of 64 constraints (base0 + k * stride) at once: every load of the K groups (key and touch
 // flag, then — touched constraints only — record, flags, scale, votes) is issued before any of them is
 // used, so a wave keeps K times the memory requests in flight.
-// (LMM_ANAT: `an` = stamp the steps into aa: lv[0] keys and touch flags, lv[1] touched records, lv[2] the rest;
-// wc[0] steps, wc[1] touched constraints)
+// (an: the steps' levels: lv[0] keys and touch flags, lv[1] touched records, lv[2] the rest; counters 0 steps,
+// 1 touched constraints)
 template <int K, bool kRdq = false>
 __device__ __forceinline__ int update_groups(const Dev& s, int64_t base0, int64_t stride, int round, double prec,
-                                             bool* touch, int* ucnt_sh = nullptr, int32_t* ulist = nullptr
-#if LMM_ANAT
-                                             , bool an = false, AnatAcc* aa = nullptr, unsigned* wc = nullptr
-#endif
-) {
+                                             bool* touch, int* ucnt_sh = nullptr, int32_t* ulist = nullptr,
+                                             Anat an = Anat()) {
   const int lane = threadIdx.x & (kWave - 1);
-#if LMM_ANAT
-  if (an) {
-    aa->at = anat_now();
-    wc[0]++;
-  }
-#endif
+  an.restart();
+  an.count(0);
   unsigned okey[K], tf[K];
 #pragma unroll
   for (int k = 0; k < K; k++) {
@@ -1573,15 +1411,13 @@ __device__ __forceinline__ int update_groups(const Dev& s, int64_t base0, int64_
     okey[k] = c < s.nC ? unsigned(s.key[c]) : kDeadKey;
     tf[k] = c < s.nC ? unsigned(s.ctouch[c]) : 0u;  // 1 = received decrements, 2 = saturated this round
   }
-#if LMM_ANAT
-  if (an) {
+  if (an.on()) {
     unsigned ks = 0;
 #pragma unroll
     for (int k = 0; k < K; k++)
       ks += okey[k] + tf[k];
-    ANAT_LVL(*aa, 0, ks);
+    an.level(0, ks);
   }
-#endif
   unsigned long long qx[K], qy[K], qz[K];
   double rem[K], use[K], bnd[K];
   int32_t ce[K], nv[K];
@@ -1603,17 +1439,15 @@ __device__ __forceinline__ int update_groups(const Dev& s, int64_t base0, int64_
       nv[k] = s.nvote[c];
     }
   }
-#if LMM_ANAT
-  if (an) {
+  if (an.on()) {
     double rs = 0.0;
 #pragma unroll
     for (int k = 0; k < K; k++) {
       rs += rem[k] + use[k] + bnd[k] + double(qx[k] + qy[k] + qz[k]) + double(ce[k] + nv[k]);
-      wc[1] += unsigned(__popcll(__ballot(okey[k] != kDeadKey && tf[k] == 1)));
+      an.count(1, unsigned(__popcll(__ballot(okey[k] != kDeadKey && tf[k] == 1))));
     }
-    ANAT_LVL(*aa, 1, rs);
+    an.level(1, rs);
   }
-#endif
   int alive = 0;
 #pragma unroll
   for (int k = 0; k < K; k++) {
@@ -1702,10 +1536,7 @@ __device__ __forceinline__ int update_groups(const Dev& s, int64_t base0, int64_
     if (lane == 0)
       s.chgbits[gbase >> 6] = word;
   }
-#if LMM_ANAT
-  if (an)
-    ANAT_LVL(*aa, 2, alive);
-#endif
+  an.level(2, alive);
   return alive;
 }
 
@@ -1719,13 +1550,9 @@ __device__ __forceinline__ int update_groups(const Dev& s, int64_t base0, int64_
 #define LMM_UPD_K 4
 #endif
 template <bool kRdq = false> __global__ void __launch_bounds__(kBlock) mm_update(Dev s, int round, double prec) {
-#if LMM_ANAT
-  unsigned long long* arec = anat_rec(s, anat_slot(s, round), ANAT_UPD);
-  const bool an = arec != nullptr;
-  AnatAcc aa{};
-  unsigned wc[2] = {0, 0};
-  const unsigned long long t_in = an ? anat_now() : 0;
-#endif
+  AnatWave aw;
+  const Anat an = aw.open(s, round, ANAT_UPD);
+  const unsigned long long t_in = an.now();
   if (s.ctl[CTL_DONE])
     return;
   if (blockIdx.x == 0 && threadIdx.x == 0)
@@ -1740,12 +1567,8 @@ template <bool kRdq = false> __global__ void __launch_bounds__(kBlock) mm_update
   const int64_t stride = int64_t(gridDim.x) * kBlock;
   for (int64_t base = (int64_t(blockIdx.x) * kBlock + threadIdx.x) & ~int64_t(kWave - 1); base < s.nC;
        base += LMM_UPD_K * stride)  // wave-uniform; LMM_UPD_K groups of 64 constraints per step, loads in flight together
-#if LMM_ANAT
-    alive += update_groups<LMM_UPD_K, kRdq>(s, base, stride, round, prec, &any_touch, &ucnt_sh, ulist, an, &aa, wc);
-  const unsigned long long t_loop = an ? anat_now() : 0;
-#else
-    alive += update_groups<LMM_UPD_K, kRdq>(s, base, stride, round, prec, &any_touch, &ucnt_sh, ulist);
-#endif
+    alive += update_groups<LMM_UPD_K, kRdq>(s, base, stride, round, prec, &any_touch, &ucnt_sh, ulist, an);
+  const unsigned long long t_loop = an.now();
   if (alive)
     atomicAdd(&alive_cnt, alive);
   __syncthreads();
@@ -1760,18 +1583,16 @@ template <bool kRdq = false> __global__ void __launch_bounds__(kBlock) mm_update
   }
   if (__syncthreads_or(any_touch) && threadIdx.x == 0)
     s.ctl[CTL_LASTR] = round;  // plain store: the last round that changed a constraint
-#if LMM_ANAT
-  if (an && (threadIdx.x & (kWave - 1)) == 0) {
-    arec[0] = t_in;
-    arec[1] = anat_now();
-    arec[2] = blockIdx.x;
-    arec[3] = t_loop;
+  if (an.on() && (threadIdx.x & (kWave - 1)) == 0) {
+    an.put(0, t_in);
+    an.put(1, an.now());
+    an.put(2, blockIdx.x);
+    an.put(3, t_loop);
     for (int f = 0; f < 3; f++)
-      arec[4 + f] = aa.lv[f];
-    arec[7] = wc[0];
-    arec[8] = wc[1];
+      an.put(4 + f, an.lv(f));
+    an.put(7, an.cnt(0));
+    an.put(8, an.cnt(1));
   }
-#endif
 }
 
 // Termination (maxmin.cpp:680): no constraint left in the light table after the last update.

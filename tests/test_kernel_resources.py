@@ -44,16 +44,24 @@ def unit_report(unit, flags):
     return kernels
 
 
-def resource_report():
-    """Merged report of every unit, and the kernel names more than one unit reports."""
+_REPORTS = {}
+
+
+def resource_report(extra=()):
+    """Merged report of every unit (compiled once per set of extra flags), and the kernel names more than one unit
+    reports."""
+    if extra in _REPORTS:
+        return _REPORTS[extra]
     units, flags = makefile_units()
     assert "lmm_hip.hip" in units and "-ffp-contract=off" in flags, (units, flags)
+    flags = flags + list(extra)
     with ThreadPoolExecutor(4) as ex:
         reports = list(ex.map(lambda u: unit_report(u, flags), units))
     kernels, twice = {}, []
     for unit, rep in zip(units, reports):
         twice += [(k, unit) for k in rep if k in kernels]
         kernels.update(rep)
+    _REPORTS[extra] = (kernels, twice)
     return kernels, twice
 
 
@@ -67,3 +75,21 @@ def test_hot_kernels_do_not_spill():
     assert all("VGPRs" in v and "VGPRs Spill" in v for v in hot.values()), hot
     bad = {k: v for k, v in hot.items() if v.get("VGPRs Spill", 0) or v.get("ScratchSize [bytes/lane]", 0)}
     assert not bad, bad
+
+
+def test_diagnostic_build_compiles_the_same_kernels():
+    """The round-anatomy build (-DLMM_ANAT=1) compiles, unit by unit (unit_report raises on a compiler error), into
+    exactly the product build's kernels, and LMM_ANAT is a preprocessor matter of lmm_dev.hpp alone: the kernels speak
+    to the probe type defined there.  (Its register counts are not asserted: the stamps cost registers, and nobody
+    times that build.)"""
+    product, _ = resource_report()
+    diag, twice = resource_report(("-DLMM_ANAT=1",))
+    assert not twice, twice
+    assert sorted(diag) == sorted(product), sorted(set(diag) ^ set(product))
+    named = []
+    for f in sorted(os.listdir(CSRC)):
+        if f.endswith("_kernels.hpp") or f.endswith(".hip"):
+            for n, line in enumerate(open(os.path.join(CSRC, f)), 1):
+                if line.lstrip().startswith("#") and "LMM_ANAT" in line:
+                    named.append((f, n, line.strip()))
+    assert not named, named
