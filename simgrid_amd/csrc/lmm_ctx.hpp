@@ -201,6 +201,8 @@ struct lmmhip_ctx {
   bool vote_diag = std::getenv("LMMHIP_VOTE_DIAG") != nullptr;  // profiling: diagnostic vote launches
   bool vote_bits = true;  // short-row vote: changed-constraint bitmap in LDS (LMMHIP_VOTE_BITS=0: the stamps' path)
   int64_t vote_bits_rows = 0;  // ... only while the alive rows (host view) are at least this many
+  bool vote_satkey = true;  // short-row vote with row records: the filter retires the rows of saturated targets
+                            // (kSatKey), the re-votes read no variable state (LMMHIP_SATKEY=0: the state-read path)
   DevPtr<unsigned> pbar;
   bool persist_prof = false;    // record barrier timestamps in the persistent launch
   DevPtr<long long> ptime;      // [2 * kPersistProfCap] last arrival / exit per barrier

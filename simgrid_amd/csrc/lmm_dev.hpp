@@ -14,7 +14,13 @@ constexpr int kWave = 64;
 constexpr int kMaxBlocks = 2048;       // 256 CUs x 8 resident 256-thread blocks; grid-stride beyond
 constexpr int kRowsPerThread = 8;      // compaction chunking
 constexpr int kCompactRows = kBlock * kRowsPerThread;
-constexpr unsigned kDeadKey = 0xFFFFu;  // > every key of a finite positive ratio (<= 0x7F80)
+// Two keys of a constraint out of the light table, both > every key of a finite positive ratio (<= 0x7F80), so every
+// minimum over keys ignores them alike.  kSatKey: it saturated — every alive row that voted for it had its variable
+// fixed in that round, so such a row is retired on the key alone; kDeadKey: never alive, or exhausted by other
+// constraints' saturations — the rows voting for it are alive and re-vote.
+constexpr unsigned kDeadKey = 0xFFFFu;
+constexpr unsigned kSatKey = 0xFFFEu;
+__host__ __device__ constexpr bool key_dead(unsigned k) { return k >= kSatKey; }
 
 // control block words (int32, zeroed at the start of every solve)
 enum : int {

@@ -65,14 +65,22 @@ static int launch_vote(lmmhip_ctx* c, int64_t r, int64_t nrows) {
         LAUNCH(7, r, (mm_vote_lane<kVBlock, true, 1>), c->n_cu, kVBlock, d, int(r));
         LAUNCH(7, r, mm_vote_diagcount, grid_for((int64_t(d.nC) + 63) / 64, kBlock), kBlock, d, int(r));
       }
-      if (d.rdq[0])
+      if (d.rdq[0] && c->vote_satkey)
+        LAUNCH(2, r, (mm_vote_lane<kVBlock, true, 0, true, true, true>), c->n_cu, kVBlock, d, int(r));
+      else if (d.rdq[0])
         LAUNCH(2, r, (mm_vote_lane<kVBlock, true, 0, true, true>), c->n_cu, kVBlock, d, int(r));
+      else if (d.crec[0] && c->vote_satkey)
+        LAUNCH(2, r, (mm_vote_lane<kVBlock, true, 0, true, false, true>), c->n_cu, kVBlock, d, int(r));
       else if (d.crec[0])
         LAUNCH(2, r, (mm_vote_lane<kVBlock, true, 0, true>), c->n_cu, kVBlock, d, int(r));
       else
         LAUNCH(2, r, (mm_vote_lane<kVBlock, true>), c->n_cu, kVBlock, d, int(r));
+    } else if (d.rdq[0] && c->vote_satkey) {
+      LAUNCH(2, r, (mm_vote_lane<kBlock, false, 0, true, true, true>), grid, kBlock, d, int(r));
     } else if (d.rdq[0]) {
       LAUNCH(2, r, (mm_vote_lane<kBlock, false, 0, true, true>), grid, kBlock, d, int(r));
+    } else if (d.crec[0] && c->vote_satkey) {
+      LAUNCH(2, r, (mm_vote_lane<kBlock, false, 0, true, false, true>), grid, kBlock, d, int(r));
     } else if (d.crec[0]) {
       LAUNCH(2, r, (mm_vote_lane<kBlock, false, 0, true>), grid, kBlock, d, int(r));
     } else {
@@ -145,6 +153,9 @@ int solve_maxmin(lmmhip_ctx* c, double prec) {
     d.useg = sg;
     d.ucnt = uc;
   }
+  // the filter retires the rows of saturated targets on the key it gathered (kSatKey, vote_waves) and the re-votes read
+  // no variable state (the row-record forms of the short-row vote).  LMMHIP_SATKEY=0: the state-read path
+  c->vote_satkey = env_int("LMMHIP_SATKEY", 1) != 0;
   c->vote_bits = env_int("LMMHIP_VOTE_BITS", 1) != 0;
   c->vote_bits_rows = env_int("LMMHIP_VOTE_BITS_ROWS", 0);
   const int gC4 = grid_for(d.nC, kBlock / kWave);

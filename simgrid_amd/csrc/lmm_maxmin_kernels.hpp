@@ -242,7 +242,9 @@ template <int G> __global__ void __launch_bounds__(kBlock) mm_vote(Dev s, int ro
     const int lt = lrow < nrows ? rtgt[lrow] : kRetired;  // streamed, row-aligned
     // re-vote when the target changed last round, unless it is still strictly below every other
     // constraint of the row (their keys only grow): then the vote stands (skey)
-    const bool lneed = lt == kUnvoted || (lt >= 0 && s.chg[lt] == prev && !(key[lt] < s.skey[buf][lrow]));
+    // (a saturated target's key, kSatKey, is below a floor of 0xFFFF: key_dead() queues its rows all the same)
+    const bool lneed = lt == kUnvoted || (lt >= 0 && s.chg[lt] == prev &&
+                                          (key_dead(key[lt]) || !(key[lt] < s.skey[buf][lrow])));
     unsigned long long mask = __ballot(lneed);
     while (mask) {  // wave-uniform
       unsigned long long m = mask;
@@ -284,7 +286,7 @@ template <int G> __global__ void __launch_bounds__(kBlock) mm_vote(Dev s, int ro
         nmin += key[ccol[j]] == mk;
       nmin = grp_isum<G>(nmin);
       const double vb = need ? s.vbound[v] : -1.0;
-      const bool live = need && mk != kDeadKey;
+      const bool live = need && !key_dead(mk);
       double minr = dinf();
       if (live && (nmin > 1 || vb > 0)) {
         if (h0 && k0 == mk)
@@ -336,13 +338,13 @@ template <int G> __global__ void __launch_bounds__(kBlock) mm_vote(Dev s, int ro
           s.vstate[v] = round + 1;  // fixed / dropped in this round
           s.x[v] = vb;
           rtgt[row] = kRetired;
-          if (t >= 0 && key[t] != kDeadKey)
+          if (t >= 0 && !key_dead(key[t]))
             atomicAdd(&s.nvote[t], mult_old);
         }
         for (uint32_t j = s.var_ptr[v] + g; j < s.var_ptr[v + 1]; j += G)
           push_decrement(s, j, vb, p);
       } else if (live && newt != t && g == 0) {
-        if (t >= 0 && key[t] != kDeadKey)
+        if (t >= 0 && !key_dead(key[t]))
           atomicAdd(&s.nvote[t], mult_old);
         atomicSub(&s.nvote[newt], mult_new);
         rtgt[row] = newt;
@@ -375,7 +377,7 @@ __global__ void __launch_bounds__(kBlock) mm_clist(Dev s, int from_all) {
   int cnt = 0;
   for (int64_t i = lo + threadIdx.x; i < hi; i += kBlock) {
     const int32_t c = from_all ? int32_t(i) : s.clist[in][i];
-    cnt += s.key[c] != kDeadKey;
+    cnt += !key_dead(s.key[c]);
   }
   cnt = grp_isum<kWave>(cnt);
   if (lane == 0)
@@ -394,7 +396,7 @@ __global__ void __launch_bounds__(kBlock) mm_clist(Dev s, int from_all) {
     int32_t c = -1;
     if (i < hi)
       c = from_all ? int32_t(i) : s.clist[in][i];
-    const bool alive = c >= 0 && s.key[c] != kDeadKey;
+    const bool alive = c >= 0 && !key_dead(s.key[c]);
     const unsigned long long m = __ballot(alive);
     __syncthreads();
     if (lane == 0)
@@ -443,7 +445,10 @@ constexpr int kFilt = LMM_KFILT;  // rows per lane per filter step (their loads 
 // stores and atomics)
 // kRdq: a constraint this re-vote made ready (nothing votes elsewhere any more) is returned in *rdq_c for the
 // caller's workgroup-wide queueing (rdq_push_lds), or queued here when rdq_c is null.
-template <int R, bool kRec = false, bool kRdq = false>
+// kSat: the caller's filter retires the rows of saturated targets itself (vote_waves, kSatRet), so a row that has
+// voted before and reaches here has an alive variable: its state is not read.  Only a row that never voted
+// (kUnvoted) still reads it.
+template <int R, bool kRec = false, bool kRdq = false, bool kSat = false>
 __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64_t row, int* st_rows,
                                          int* st_elems, const uint16_t* __restrict__ key, int* rdq_c = nullptr,
                                          Anat an = Anat()) {
@@ -469,7 +474,7 @@ __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64
   }
   an.level(0, b + e + uint32_t(t) + uint32_t(cv));
   const int v = rvar(cv);
-  const int32_t vst = s.vstate[v];
+  const int32_t vst = !kSat || t == kUnvoted ? s.vstate[v] : 0;
   const bool bnd = rbounded(cv);
   const double vb = bnd ? s.vbound[v] : -1.0;
   const double p = bnd ? s.pen[v] : 1.0;  // read below only when vb > 0
@@ -511,7 +516,7 @@ __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64
   for (uint32_t j = b + R; j < e; j++)
     mk = min(mk, (unsigned)key[ccol[j]]);
   an.level(3, mk + kt);
-  if (mk == kDeadKey) {  // every constraint of v left the light table: v stays at 0
+  if (key_dead(mk)) {  // every constraint of v left the light table: v stays at 0
     s.vstate[v] = round + 1;  // fixed / dropped in this round
     rtgt[row] = kRetired;
     return;
@@ -571,7 +576,7 @@ __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64
     s.vstate[v] = round + 1;  // fixed / dropped in this round
     s.x[v] = vb;
     rtgt[row] = kRetired;
-    if (t >= 0 && kt != kDeadKey)
+    if (t >= 0 && !key_dead(kt))
       atomicAdd(&s.nvote[t], mult_old);
     for (uint32_t j = s.var_ptr[v]; j < s.var_ptr[v + 1]; j++)
       push_decrement(s, j, vb, p);
@@ -596,7 +601,7 @@ __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64
   skey[row] = uint16_t(row_floor(sk, mk, vb, p));
   if (newt == t)
     return;
-  if (t >= 0 && kt != kDeadKey)
+  if (t >= 0 && !key_dead(kt))
     atomicAdd(&s.nvote[t], mult_old);
   if (kRdq) {
     const int old = atomicSub(&s.nvote[newt], mult_new);
@@ -625,6 +630,11 @@ __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64
 // target was touched at all (chg stamp).  Returns the rows this wave queued (lane-uniform).
 // kDiag (measurement only, LMMHIP_VOTE_DIAG): 1 = the filter alone (rows queued, none resolved), with
 // per-round counters of target-changed / sensitive / queued rows in vstat's kDiagSlot.
+// kSatRet: a row whose target saturated last round (its gathered key is kSatKey) is not queued: its variable was fixed
+// by that saturation — a constraint saturates only when every alive element on it votes for it, and claims every alive
+// variable on it, so "the row's target saturated" and "the row's variable was fixed by a saturation" are one event —
+// and the lane stores kRetired itself.  The re-votes (vote_row, kSat) then read no variable state.  The diagnostic
+// filter (kDiag 1) stays read-only and counts such rows in word 7 of its record (they are part of its queued count).
 constexpr int kQW = 2 * kWave;  // per-wave queue capacity
 
 // The wave's row range [wlo, whi) of the workgroup's rows [lo, hi).
@@ -638,7 +648,7 @@ __device__ __forceinline__ void vote_wave_range(int64_t lo, int64_t hi, int64_t&
 
 // an: the filter steps and re-vote batches of this wave (lv[6] filter loads, lv[7] filter gathers, lv[8] re-vote
 // batches; counters 0 steps, 1 batches); ar: vote_row's levels.
-template <bool kBits, int R, int F, int kDiag, bool kRec = false, bool kRdq = false>
+template <bool kBits, int R, int F, int kDiag, bool kRec = false, bool kRdq = false, bool kSatRet = false>
 __device__ __forceinline__ int vote_waves(const Dev& s, int buf, int round, int64_t lo, int64_t hi,
                                           const uint64_t* bits, int* qw, int* st_rows, int* st_elems,
                                           const uint16_t* __restrict__ key, RdqLds* rql = nullptr, Anat an = Anat(),
@@ -651,7 +661,8 @@ __device__ __forceinline__ int vote_waves(const Dev& s, int buf, int round, int6
   const uint16_t prev = uint16_t(round - 1);
   const unsigned long long below = (1ull << lane) - 1;
   int qn = 0, nq = 0;
-  int dg[4] = {0, 0, 0, 0};  // kDiag 1: target-changed / sensitive / queued / queued sensitive rows of this lane
+  // kDiag 1: target-changed / sensitive / queued / queued sensitive / saturated-target rows of this lane
+  int dg[5] = {0, 0, 0, 0, 0};
   for (int64_t base = wlo; base < whi; base += int64_t(F) * kWave) {  // wave-uniform
     int tt[F];
     unsigned sk[F];
@@ -696,9 +707,13 @@ __device__ __forceinline__ int vote_waves(const Dev& s, int buf, int round, int6
     for (int u = 0; u < F; u++) {
       bool need = tt[u] == kUnvoted;  // (rows >= whi carry kRetired)
       if (ch[u])
-        need = !(kt[u] < sk[u]);
+        need = key_dead(kt[u]) || !(kt[u] < sk[u]);
       else if (kBits && cg[u] == prev)
         need = true;
+      if (kSatRet && kDiag == 0 && ch[u] && kt[u] == kSatKey) {  // fixed with its target: retired here
+        s.rtgt[buf][base + u * kWave + lane] = kRetired;
+        need = false;
+      }
       needm |= unsigned(need) << u;
       if (kDiag == 1) {
         dg[0] += ch[u];
@@ -708,6 +723,7 @@ __device__ __forceinline__ int vote_waves(const Dev& s, int buf, int round, int6
           atomicOr(reinterpret_cast<unsigned long long*>(&s.flagbits[tt[u] >> 6]), 1ull << (tt[u] & 63));
           dg[3] += sk[u] == 0;
         }
+        dg[4] += ch[u] && kt[u] == kSatKey;
       }
     }
 #pragma unroll 1
@@ -727,7 +743,7 @@ __device__ __forceinline__ int vote_waves(const Dev& s, int buf, int round, int6
         an.restart();
         an.count(1);
         if (kDiag == 0)
-          vote_row<R, kRec, kRdq>(s, buf, round, row, st_rows, st_elems, key, &pc, ar);
+          vote_row<R, kRec, kRdq, kSatRet>(s, buf, round, row, st_rows, st_elems, key, &pc, ar);
         if (kRdq && kDiag == 0)
           rdq_push_lds(s, pc, round, rql);
         an.level(8, 0u);
@@ -741,17 +757,17 @@ __device__ __forceinline__ int vote_waves(const Dev& s, int buf, int round, int6
   }
   int pc = -1;
   if (kDiag == 0 && lane < qn)
-    vote_row<R, kRec, kRdq>(s, buf, round, qw[lane], st_rows, st_elems, key, &pc, ar);
+    vote_row<R, kRec, kRdq, kSatRet>(s, buf, round, qw[lane], st_rows, st_elems, key, &pc, ar);
   if (kRdq && kDiag == 0)
     rdq_push_lds(s, pc, round, rql);
   if (an.on() && qn > 0)
     an.level(8, 0u);
   if (kDiag == 1 && s.vstat && round < kStatRounds) {
     int32_t* d = s.vstat + 2 * (int64_t(round) * kMaxBlocks + kDiagSlot);
-    for (int k = 0; k < 4; k++) {
+    for (int k = 0; k < 5; k++) {
       const int t = grp_isum<kWave>(dg[k]);
       if (lane == 0 && t)
-        atomicAdd(&d[k == 3 ? 6 : k], t);
+        atomicAdd(&d[k == 3 ? 6 : k == 4 ? 7 : k], t);
     }
   }
   return nq + qn;
@@ -825,7 +841,7 @@ __global__ void __launch_bounds__(kBlock) mm_vote_diagcount(Dev s, int round) {
 constexpr int kVBlock = 1024;
 // (Round 5 measured the first filter step's loads issued before the bitmap copy: 24.313 / 24.390 ms against 24.340 /
 // 24.309 without, profiles/r05_ab_c2_spec2.json — neutral, the copy is not the vote's critical path; removed.)
-template <int B, bool kBits, int kDiag = 0, bool kRec = false, bool kRdq = false>
+template <int B, bool kBits, int kDiag = 0, bool kRec = false, bool kRdq = false, bool kSatRet = false>
 __global__ void __launch_bounds__(B) mm_vote_lane(Dev s, int round) {
   AnatWave aw, awr;  // (the wave's filter steps and batches; vote_row's levels)
   const Anat an = kDiag == 0 ? aw.open(s, round, ANAT_VOTE) : Anat();
@@ -863,8 +879,9 @@ __global__ void __launch_bounds__(B) mm_vote_lane(Dev s, int round) {
   }
   int nq = 0;
   if (lo < hi)
-    nq = vote_waves<kBits, 8, kFilt, kDiag, kRec, kRdq>(s, buf, round, lo, hi, bits, q + (threadIdx.x / kWave) * kQW,
-                                                        &st_rows, &st_elems, s.key, &rql, an, ar);
+    nq = vote_waves<kBits, 8, kFilt, kDiag, kRec, kRdq, kSatRet>(s, buf, round, lo, hi, bits,
+                                                                 q + (threadIdx.x / kWave) * kQW, &st_rows, &st_elems,
+                                                                 s.key, &rql, an, ar);
   if (kRdq && kDiag == 0)
     rdq_flush_lds(s, round, &rql);
   if (an.on()) {  // the wave's record (vote_row's levels: the slowest lane of the wave)
@@ -920,7 +937,7 @@ __global__ void __launch_bounds__(kBlock) mm_ready(Dev s) {
   const int64_t hi = lo + chunk < n ? lo + chunk : n;
   for (int64_t i = lo + threadIdx.x; i < hi; i += kBlock) {
     const int32_t c = s.clist[cb][i];
-    if (s.key[c] != kDeadKey && s.nvote[c] == 0)
+    if (!key_dead(s.key[c]) && s.nvote[c] == 0)
       s.ready[lo + atomicAdd(&cnt, 1)] = c;
   }
   __syncthreads();
@@ -1133,7 +1150,7 @@ __device__ __forceinline__ bool sat_block(const Dev& s, int round, const int32_t
     int32_t c = -1;
     if (i < n)
       c = cl ? cl[i] : int32_t(i);
-    const bool rdy = c >= 0 && s.key[c] != kDeadKey && s.nvote[c] == 0;
+    const bool rdy = c >= 0 && !key_dead(s.key[c]) && s.nvote[c] == 0;
     const int nch = rdy ? int((s.cnst_ptr[c + 1] - s.cnst_ptr[c] + kWave - 1) / kWave) : 0;
     int ia = rdy, ib = nch;  // block exclusive scans of (ready, chunks)
 #pragma unroll
@@ -1368,7 +1385,7 @@ template <int K> __global__ void __launch_bounds__(kBlock) mm_saturate_q(Dev s, 
     an.level(6, cur.r + double(cur.kc + unsigned(cur.nv) + cur.cb + cur.ce + unsigned(cur.dup)));
     const CandSt nxt = state_of(cnext);  // (issued before this task's chunk loads)
     cnext = g + 2 * nwaves < T ? cand_of(g + 2 * nwaves) : -1;
-    if (cur.kc != kDeadKey && cur.nv == 0) {  // (the round's CTL_LASTR: mm_update, from the constraints saturated here)
+    if (!key_dead(cur.kc) && cur.nv == 0) {  // (the round's CTL_LASTR: mm_update, from the constraints saturated here)
       saturate_one_pre<K>(s, cur.c, k, round, lane, wpre[w], cur.r, cur.cb, cur.ce, cur.dup, an);
     }
     cur = nxt;
@@ -1427,7 +1444,7 @@ __device__ __forceinline__ int update_groups(const Dev& s, int64_t base0, int64_
     qx[k] = qy[k] = qz[k] = 0;
     rem[k] = use[k] = bnd[k] = 0.0;
     ce[k] = nv[k] = 0;
-    if (okey[k] != kDeadKey && tf[k] == 1) {  // an untouched constraint keeps its record as it is
+    if (!key_dead(okey[k]) && tf[k] == 1) {  // an untouched constraint keeps its record as it is
       const CstRec* rec = s.cst + c;
       qx[k] = rec->drem;
       qy[k] = rec->duse;
@@ -1444,7 +1461,7 @@ __device__ __forceinline__ int update_groups(const Dev& s, int64_t base0, int64_
 #pragma unroll
     for (int k = 0; k < K; k++) {
       rs += rem[k] + use[k] + bnd[k] + double(qx[k] + qy[k] + qz[k]) + double(ce[k] + nv[k]);
-      an.count(1, unsigned(__popcll(__ballot(okey[k] != kDeadKey && tf[k] == 1))));
+      an.count(1, unsigned(__popcll(__ballot(!key_dead(okey[k]) && tf[k] == 1))));
     }
     an.level(1, rs);
   }
@@ -1455,7 +1472,7 @@ __device__ __forceinline__ int update_groups(const Dev& s, int64_t base0, int64_
     if (gbase >= s.nC)  // wave-uniform
       break;
     const int64_t c = gbase + lane;
-    const bool live0 = okey[k] != kDeadKey;
+    const bool live0 = !key_dead(okey[k]);
     const bool sat = live0 && tf[k] == 2;
     const bool live = live0 && !sat;
     const bool tch = live && tf[k] == 1;
@@ -1483,7 +1500,7 @@ __device__ __forceinline__ int update_groups(const Dev& s, int64_t base0, int64_
     CstRec* rec = s.cst + c;
     if (sat) {
       *touch = true;  // (a saturation this round: the round's CTL_LASTR, set here instead of by every ready task)
-      s.key[c] = kDeadKey;
+      s.key[c] = kSatKey;  // (its voters were all fixed with it: the next filter retires their rows on this key)
       s.cexp[c] = kCexpDead;
       s.chg[c] = uint16_t(round);
       s.ctouch[c] = 0;
