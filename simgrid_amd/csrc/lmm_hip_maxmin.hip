@@ -281,7 +281,10 @@ int solve_maxmin(lmmhip_ctx* c, double prec) {
       ncl = h[CTL_NCL0 + h[CTL_CB]];
       nrows = h[CTL_NROWS + h[CTL_BUF]];
     }
-    if (r > max_rounds)
+    // the guard counts the rounds the device has RUN without finishing (CTL_ROUNDS of the newest words), not the rounds
+    // queued: the polls are one chunk behind, so a system of 3 variables and 3 rounds has 6 rounds queued when the
+    // words of its first two arrive, and counting those failed it
+    if (h && h[CTL_ROUNDS] > max_rounds)
       return fail(LMMHIP_E_NOCONVERGE, "maxmin round guard tripped");
     if (chunk < chunk_max)
       chunk = std::min(2 * chunk, chunk_max);
@@ -305,7 +308,10 @@ int solve_maxmin_frontier(lmmhip_ctx* c, double prec) {
   if (!c->vote_diag)  // per-round diagnostic counters only on request (LMMHIP_VOTE_DIAG): they cost atomics
     d.vstat = nullptr;
   const int64_t nnz = std::max<int64_t>(d.nnz, 1);
-  const int nblk = int((int64_t(d.nC) + kFB - 1) / kFB);  // fr_update / fr_vote (/ fr_sat<256>) workgroups
+  // fr_update / fr_vote (/ fr_sat<256>) workgroups; one for a system without constraints (every variable disabled
+  // or on zero-bound constraints only: nothing flattened), whose first round then finds nothing alive — a grid of
+  // zero workgroups is a launch error
+  const int nblk = int(std::max<int64_t>(1, (int64_t(d.nC) + kFB - 1) / kFB));
   const int nblkS = int(std::max<int64_t>(1, (int64_t(d.nC) + kFS - 1) / kFS));  // fr_sat workgroups
   int2* cs = nullptr;
   int32_t* md = nullptr;
@@ -403,7 +409,7 @@ int solve_maxmin_frontier(lmmhip_ctx* c, double prec) {
       return rc;
     if (h && h[CTL_DONE])
       break;
-    if (r > max_rounds)
+    if (h && h[CTL_ROUNDS] > max_rounds)  // (rounds run, not rounds queued: see solve_maxmin)
       return fail(LMMHIP_E_NOCONVERGE, "maxmin round guard tripped");
     if (chunk < chunk_cap)
       chunk = std::min(2 * chunk, chunk_cap);

@@ -350,6 +350,118 @@ def random_script(seed, n_cnst=30, n_var=60, max_el=6, fatpipe_p=0.1, bounded_p=
     return ops
 
 
+def scale_script(ops, k):
+    """`ops` with every bound multiplied by 2^k: `cnst` bounds, positive `var` bounds, `vbound` and `cbound` values.
+    Weights, penalties and -1.0 ("no bound") stay.  The multiplication is exact in fp64 (no result of the scripts
+    above leaves the normal range for |k| <= 900), so the max-min solution of the scaled script is ldexp(x, k) of
+    the unscaled one wherever the solver's decisions do not depend on the magnitude."""
+    import math
+
+    out = []
+    for op in ops:
+        t = op[0]
+        if t == "cnst":
+            op = (t, op[1], math.ldexp(op[2], k))
+        elif t == "var" and op[3] > 0:
+            op = (t, op[1], op[2], math.ldexp(op[3], k), op[4])
+        elif t in ("vbound", "cbound") and op[2] > 0:
+            op = (t, op[1], math.ldexp(op[2], k))
+        out.append(op)
+    return out
+
+
+def spread_script(ops, seed, span):
+    """`ops` with bounds of mixed magnitudes: constraint c's bound (its `cnst` op and its later `cbound` updates) is
+    multiplied by 2^e_c, every positive `var` bound and every `vbound` by a power of two of its own, all exponents
+    drawn from random.Random(seed) in [0, span].  No exponent is negative: bound levels stay as far apart as in
+    `ops`, so the reference's absolute 1e-5 window on them (domain and magnitudes) plays no larger part."""
+    import math
+
+    rng = random.Random(seed)
+    e_c = {}
+    out = []
+    for op in ops:
+        t = op[0]
+        if t == "cnst":
+            e_c[op[1]] = rng.randint(0, span)
+            op = (t, op[1], math.ldexp(op[2], e_c[op[1]]))
+        elif t == "cbound":
+            op = (t, op[1], math.ldexp(op[2], e_c[op[1]]))
+        elif t == "var" and op[3] > 0:
+            op = (t, op[1], op[2], math.ldexp(op[3], rng.randint(0, span)), op[4])
+        elif t == "vbound" and op[2] > 0:
+            op = (t, op[1], math.ldexp(op[2], rng.randint(0, span)))
+        out.append(op)
+    return out
+
+
+def unbounded_script(seed, **kw):
+    """random_script without any variable bound: bounded_p = 0 and the `vbound` updates removed (the scripts that
+    scale DOWN exactly, see scale_script and tests/test_oracle.py)."""
+    return [op for op in random_script(seed, bounded_p=0.0, **kw) if op[0] != "vbound"]
+
+
+# ---------------------------------------------------------------------------------------------
+# Scripted systems that force each vote kernel (tests/test_gpu_engine_scripts.py, tests/test_gpu_magnitudes.py).
+# finish_flat picks the vote kernel from the flattened mean row length (elements per variable): lane vote with groups
+# of 4 (<= 4) or 8 (<= 8), mm_vote<16> (<= 16), mm_vote<32> (<= 32), mm_vote<64> above.  Each shape names the
+# bracket (lo, hi] it has to fall in; the tests assert it, on the CPU and again where the device solves it.
+# ---------------------------------------------------------------------------------------------
+#
+# Concurrency limits are on for even seeds.  random_script draws limits of 2..6 on half the constraints, and a variable
+# is staged (disabled) as soon as one of its constraints has no slot left: with limits on, nearly every long row is
+# staged and what is flattened has a mean row of 6..13 elements whatever max_el is (measured for max_el up to 150).
+# So the long-row shapes R16 / R32 / R64 take three odd seeds (no limits; R64 skips seed 5, whose solution has no
+# variable at its bound); R4, R8 and WIDE take seeds 0, 1, 2.
+# R4L and R8L are R4 and R8 with more than 4096 flattened variables and constraints, the size below which the round
+# engine never compacts its alive rows nor rewrites its constraint list (solve_maxmin, chunk_end); the host's view of
+# the row count is refreshed at every poll, so they start well above it (with 4369 rows the first poll already reports
+# fewer than 4096 and no row compaction is ever launched).  R8S is a quarter of
+# R8, for the test that builds the system five times over (re-solves of one context against fresh contexts).
+SCRIPT_UPDATES = dict(frees=20, penalty_updates=30, bound_updates=30)
+ENGINE_SHAPES = {
+    "R4": (dict(n_cnst=200, n_var=1500, max_el=3), (0.0, 4.0), (0, 1, 2)),
+    "R8": (dict(n_cnst=300, n_var=3000, max_el=12), (4.0, 8.0), (0, 1, 2)),
+    "R16": (dict(n_cnst=150, n_var=1200, max_el=28), (8.0, 16.0), (1, 3, 5)),
+    "R32": (dict(n_cnst=150, n_var=800, max_el=58), (16.0, 32.0), (1, 3, 5)),
+    "R64": (dict(n_cnst=150, n_var=600, max_el=100), (32.0, float("inf")), (1, 3, 7)),
+    # few constraints of very high degree, half of them FATPIPE
+    "WIDE": (dict(n_cnst=6, n_var=2000, max_el=3, fatpipe_p=0.5), (0.0, 4.0), (0, 1, 2)),
+    "R4L": (dict(n_cnst=5000, n_var=9000, max_el=3), (0.0, 4.0), (1,)),
+    "R8L": (dict(n_cnst=4500, n_var=6000, max_el=12), (4.0, 8.0), (1,)),
+    "R8S": (dict(n_cnst=100, n_var=700, max_el=12), (4.0, 8.0), (0, 1)),
+}
+
+
+def engine_script(shape, seed, unbounded=False):
+    """The script of ENGINE_SHAPES[shape] for `seed`: frees, penalty and bound updates, concurrency limits on even
+    seeds.  unbounded: the unbounded_script of the same arguments."""
+    kw = dict(ENGINE_SHAPES[shape][0], conc_limits=(seed % 2 == 0), **SCRIPT_UPDATES)
+    return unbounded_script(seed, **kw) if unbounded else random_script(seed, **kw)
+
+
+def mean_row(flat):
+    """Flattened elements per variable of a multi.export_flat() result: what finish_flat picks the vote kernel by."""
+    return len(flat.cnst_idx) / len(flat.penalty)
+
+
+def script_features(ops):
+    """What a script carries, counted on the op list: FATPIPE constraints, zero-bound constraints (as created),
+    zero-weight elements, duplicate (constraint, variable) pairs among the `expand` ops, zero-penalty variables
+    (created so, or set so by a `penalty` update)."""
+    pairs = [(op[1], op[2]) for op in ops if op[0] == "expand"]
+    return dict(fatpipe=sum(op[0] == "unshare" for op in ops),
+                zero_bound=sum(op[0] == "cnst" and op[2] == 0.0 for op in ops),
+                zero_weight=sum(op[0] == "expand" and op[3] == 0.0 for op in ops),
+                duplicates=len(pairs) - len(set(pairs)),
+                zero_penalty=sum((op[0] == "var" or op[0] == "penalty") and op[2] == 0.0 for op in ops))
+
+
+def fixed_at_bound(vs):
+    """Variables of a solved system that sit at their own bound (bound > 0 and value == bound)."""
+    return sum(1 for v in vs.values() if v.get_bound() > 0 and v.get_value() == v.get_bound())
+
+
 def replay(M, ops, selective=False, kind=0, sys_=None, cs=None, vs=None):
     s = sys_ if sys_ is not None else M.System(selective, kind)
     cs = {} if cs is None else cs
