@@ -2,7 +2,8 @@
 //
 //   lmm_hip.hip           context, flat allocation and upload, lmmhip_solve, setters, getters, profile exports;
 //                         owns lmm_common_kernels.hpp and lmm_cc_kernels.hpp
-//   lmm_hip_maxmin.hip    the round, frontier, persistent and batch max-min engines
+//   lmm_hip_maxmin.hip    the round, frontier, persistent and batch max-min engines; the first two are chains of
+//                         launches: a plan per solve (RoundPlan / FrontierPlan below) and one chunk driver (run_chunks)
 //   lmm_hip_fair.hip      FairBottleneck: the chunked engine, its sharded protocol, and the batch engine
 //   lmm_hip_resident.hip  the resident mirror, the device flatten and the value fetches
 //   lmm_hip_step.hip      the model-side action state
@@ -21,6 +22,7 @@
 
 #include "../../include/lmm/lmm_hip.h"
 #include "lmm_dev.hpp"
+#include "lmm_chunk.hpp"
 
 using namespace lmmdev;
 
@@ -128,6 +130,31 @@ struct FlatBufs {
 struct RoundEngine {
   Scr crec[3], rdq[2], rqst, useg, ucnt;
 };
+// What one round-engine solve launches (round_plan: the context, the system's sizes and the environment, read once per
+// solve — tests change the environment between solves); const from there on, handed to everything that launches.
+using VoteKernel = void (*)(Dev, int);          // (s, round)
+using SatKernel = void (*)(Dev, int, int);      // (s, round, segments)
+using UpdKernel = void (*)(Dev, int, double);   // (s, round, prec)
+struct RoundPlan {
+  // mode: row records (short rows, LMMHIP_CREC); with them the ready queue in place of the mm_ready pass (LMMHIP_RDQ)
+  // and the filter retiring the rows of saturated targets (LMMHIP_SATKEY)
+  bool crec = false, rdq = false, satkey = false;
+  // the vote: the LDS-bitmap form (null: never; one 1024-thread workgroup per CU) while the alive rows (host view) are
+  // at least vote_bits_rows, else the scan form (one lane per row of the work queue / mm_vote<G>)
+  VoteKernel vote_bitmap = nullptr, vote_scan = nullptr;
+  int64_t vote_bits_rows = 0;
+  SatKernel saturate = nullptr;  // mm_saturate<K> / mm_saturate_q<K>
+  int sat_waves = 4;             // its K: waves per ready constraint
+  UpdKernel update = nullptr;    // mm_update<rdq>
+  // grids and caps
+  int g_init_c = 1, g_c = 1;  // mm_init_cnsts (a wave per constraint), thread per constraint
+  int g_upd = 1;              // mm_update and mm_done's argument: capped identity grid, or the ready-queue segments'
+  int cap_sat = 0, sat_max = 0;  // saturation: grid cap (0: none), block cap of the uncapped grid
+  // cadences: compaction of the alive rows (every cmp_every rounds, rewritten under cmp_pct % alive), constraint list
+  int cmp_every = 48, cmp_pct = 75, cl_every = 8;
+  ChunkPolicy chunk;
+  int64_t tail_rows = 0, tail_cnst = 0;  // the solve is in its tail at this many alive rows / listed constraints
+};
 int solve_maxmin(lmmhip_ctx* c, double prec);
 
 // frontier engine (lmm_hip_maxmin.hip, lmm_frontier_kernels.hpp): CSR -> CSC map of the uploaded structure, vote
@@ -136,6 +163,18 @@ struct FrontierEngine {
   Scr c2s, slot, minfl, qa, qb, qn, md, pvb, key;
   bool map_ok = false;
   int maxdeg = 0;
+};
+// What one frontier solve launches (frontier_plan, like RoundPlan; built once the CSR -> CSC map has its largest degree)
+struct FrontierPlan {
+  int nblk = 1, nblk_sat = 1;  // fr_update / fr_vote (/ fr_sat<256>) workgroups, fr_sat<kFS> workgroups
+  int bigch = 1, bigw = 1;     // fr_sat_big: constraints of more CSC chunks than bigch, bigw waves each
+  bool big = false;            // ... and whether the system has one
+  int g_big = 1;
+  bool long_rows = false;      // fr_vote<16> instead of <8>
+  int spb = 1;                 // fr_vote: segments per workgroup
+  int sat_b = 256;             // fr_sat workgroup: 256 threads or kFS
+  int upd_spec = 0;            // fr_update: state loaded with the key
+  ChunkPolicy chunk;
 };
 int solve_maxmin_frontier(lmmhip_ctx* c, double prec);
 
@@ -199,10 +238,6 @@ struct lmmhip_ctx {
   int engine = LMMHIP_ENGINE_AUTO;
   int sat_waves = 1;  // waves per ready constraint in mm_saturate (mean 64-element CSC chunks, 1/2/4)
   bool vote_diag = std::getenv("LMMHIP_VOTE_DIAG") != nullptr;  // profiling: diagnostic vote launches
-  bool vote_bits = true;  // short-row vote: changed-constraint bitmap in LDS (LMMHIP_VOTE_BITS=0: the stamps' path)
-  int64_t vote_bits_rows = 0;  // ... only while the alive rows (host view) are at least this many
-  bool vote_satkey = true;  // short-row vote with row records: the filter retires the rows of saturated targets
-                            // (kSatKey), the re-votes read no variable state (LMMHIP_SATKEY=0: the state-read path)
   DevPtr<unsigned> pbar;
   bool persist_prof = false;    // record barrier timestamps in the persistent launch
   DevPtr<long long> ptime;      // [2 * kPersistProfCap] last arrival / exit per barrier
@@ -251,7 +286,6 @@ struct lmmhip_ctx {
   int64_t res_nE = 0, res_nV = 0, res_nC = 0;  // host table sizes of the last delta batch
   bool res_flat = false;                        // the uploaded system came from lmmhip_res_flatten
   FlatBufs fb_last{};
-  int tune_upd = 0, tune_sat = 0;
   PinPtr<double> pin_vals;  // pinned host staging of lmmhip_res_values_pinned
   PinPtr<uint8_t> pin_rst;  // (lmmhip_res_values_pinned only: the sliced fetch marks kept slots in the values)
   int64_t pin_cap = 0, pin_rst_cap = 0;  // capacities of pin_vals / pin_rst (elements)

@@ -190,6 +190,9 @@ struct Dev {
   unsigned long long* fq_a;  // [nnz] re-vote queue, one segment per fr_update workgroup: variable | target << 32
   unsigned long long* fq_b;  // [nnz]   and the variable's CSR row (begin | end << 32)
   int32_t* fq_n;             // [nC / kFB + 1] queued variables per segment
+  // The next five are the round engine's modes.  solve_maxmin fills them in its own copy of the Dev (round_buffers);
+  // the context's Dev (lmmhip_ctx::d) never carries them — they are null there for its whole life — so no other
+  // engine, getter or fallback re-run can see a stale one.
   int32_t* rdq[2];   // round engine, short rows (LMMHIP_RDQ): constraints the vote made ready, by round parity
   int32_t* rqst;     // [nC] the round a constraint was last queued for (one entry per constraint and round)
   int32_t* useg;     // [blocks x kUSeg] the update's ready candidates for the next round, a segment per workgroup

@@ -1,5 +1,10 @@
 // lmm_hip_maxmin.hip — the max-min engines of lmmhip_solve (lmm_ctx.hpp): the multi-launch round engine, the
 // frontier engine, the persistent engine with its fallback, and the block-diagonal batch engine.
+//
+// The round engine and the frontier engine are chains of launches and share their host side: round_plan / frontier_plan
+// build what a solve will launch (mode, kernels, grids, cadences, chunk policy: RoundPlan / FrontierPlan in lmm_ctx.hpp)
+// once per solve and read every environment knob of the two engines; run_chunks owns the chunk / poll / guard loop
+// (policy arithmetic: lmm_chunk.hpp).  Each engine works on its own copy of the context's Dev.
 #include <cstring>
 
 #include <map>
@@ -35,101 +40,89 @@ void persist_ctx_ref(int device, int delta) {
   }
 }
 
-// Chunk length under a round-count hint: a chunk that would cross the hinted end E is cut to end at it, and the
-// caller waits for that chunk before queueing more (*stop), so a solve as long as the previous one runs no returning
-// rounds after its last one; a longer one pays one host round trip there, a shorter one is caught by the usual polls.
-// Consecutive solves of a simulation change little, so their round counts do too.  LMMHIP_ROUND_HINT=0: off.
-static int round_hint_chunk(int64_t r, int chunk, int64_t hint, bool* stop) {
-  *stop = false;
-  if (hint > r && r + chunk >= hint) {
-    *stop = true;
-    return int(hint - r);
+// ---- the round-chain engines: the round engine and the frontier engine --------------------------------------------
+// Both run as a chain of launches, a chunk of rounds per pipelined termination poll.  A solve is: allocate, build its
+// plan (every environment knob of the engine is read there, once per solve, and nowhere else), drive the chunks.
+
+// The chunk / poll / guard loop of both engines.  Per chunk: the chunk's length (ChunkPolicy, cut at the hinted end:
+// round_hint_chunk), round_launches(r) for each of its rounds, chunk_end(r) behind them (r: the rounds queued so far),
+// the poll's mm_ctl_out (CtlPoll::step), then — on the newest control words the host has, one chunk behind, null before
+// the first have arrived — the done test, in_tail(words) (the engine refreshes its view of the sizes there and says
+// whether the solve is in its tail), the round guard and the next chunk's length.  Termination polls are pipelined
+// (CtlPoll): a chunk queued after the last round is a run of launches that return at once (CTL_DONE).  Ends with the
+// final words in c->h_ctl (the queued tail has run: final words for the stats and the caller's hint).
+template <class Rounds, class ChunkEnd, class InTail>
+static int run_chunks(lmmhip_ctx* c, const Dev& d, const ChunkPolicy& p, Rounds&& round_launches, ChunkEnd&& chunk_end,
+                      InTail&& in_tail) {
+  // Every round fixes at least one variable (DESIGN.md §3, progress), so nV + 2 rounds bound it.
+  const int64_t max_rounds = int64_t(d.nV) + 2;
+  CtlPoll poll;
+  if (int rc = poll.init(c))
+    return rc;
+  int chunk = p.first;
+  for (int64_t r = 0;;) {
+    bool stop = false;
+    const int n = round_hint_chunk(r, chunk, p.hint, &stop);
+    for (int k = 0; k < n; k++, r++)
+      if (int rc = round_launches(r))
+        return rc;
+    if (int rc = chunk_end(r))
+      return rc;
+    const int32_t* h = nullptr;
+    if (int rc = poll.step(d, r, stop, &h))
+      return rc;
+    if (h && h[CTL_DONE])
+      break;
+    const bool tail = in_tail(h);
+    // the guard counts the rounds the device has RUN without finishing (CTL_ROUNDS of the newest words), not the rounds
+    // queued: the polls are one chunk behind, so a system of 3 variables and 3 rounds has 6 rounds queued when the
+    // words of its first two arrive, and counting those failed it
+    if (h && h[CTL_ROUNDS] > max_rounds)
+      return fail(LMMHIP_E_NOCONVERGE, "maxmin round guard tripped");
+    chunk = chunk_grow(chunk, p, tail);
   }
-  return chunk;
+  return poll_ctl(c);
 }
 
-// The alive-row buffer in use is read by the vote on the device (ctl CTL_BUF); nrows (an upper bound of its
-// rows, refreshed at every poll) only sizes the grid-stride variants' grids.
-static int launch_vote(lmmhip_ctx* c, int64_t r, int64_t nrows) {
-  const Dev& d = c->d;
-  const int G = c->group;
-  const int grid = grid_for(nrows, kBlock);  // one lane per row in the work-queue scan
-  switch (G) {
-  case 4:
-  case 8:  // short rows: one lane per row (more gathers in flight per wave)
-    // the LDS bitmap of changed constraints (one 1024-thread workgroup per CU); below LMMHIP_VOTE_BITS_ROWS alive rows
-    // (host view, A/B knob; 0 = always) the change stamps gathered per row instead: no ~125-KB copy per CU
-    if (int64_t(d.nC) <= int64_t(kBitWords) * 64 && c->vote_bits && nrows >= c->vote_bits_rows) {
-      if (c->profiling && c->vote_diag) {  // measurement: bitmap load alone, filter alone (slot 7)
-        LAUNCH(7, r + 1000000, (mm_vote_lane<kVBlock, true, 2>), c->n_cu, kVBlock, d, int(r));
-        LAUNCH(7, r, (mm_vote_lane<kVBlock, true, 1>), c->n_cu, kVBlock, d, int(r));
-        LAUNCH(7, r, mm_vote_diagcount, grid_for((int64_t(d.nC) + 63) / 64, kBlock), kBlock, d, int(r));
-      }
-      if (d.rdq[0] && c->vote_satkey)
-        LAUNCH(2, r, (mm_vote_lane<kVBlock, true, 0, true, true, true>), c->n_cu, kVBlock, d, int(r));
-      else if (d.rdq[0])
-        LAUNCH(2, r, (mm_vote_lane<kVBlock, true, 0, true, true>), c->n_cu, kVBlock, d, int(r));
-      else if (d.crec[0] && c->vote_satkey)
-        LAUNCH(2, r, (mm_vote_lane<kVBlock, true, 0, true, false, true>), c->n_cu, kVBlock, d, int(r));
-      else if (d.crec[0])
-        LAUNCH(2, r, (mm_vote_lane<kVBlock, true, 0, true>), c->n_cu, kVBlock, d, int(r));
-      else
-        LAUNCH(2, r, (mm_vote_lane<kVBlock, true>), c->n_cu, kVBlock, d, int(r));
-    } else if (d.rdq[0] && c->vote_satkey) {
-      LAUNCH(2, r, (mm_vote_lane<kBlock, false, 0, true, true, true>), grid, kBlock, d, int(r));
-    } else if (d.rdq[0]) {
-      LAUNCH(2, r, (mm_vote_lane<kBlock, false, 0, true, true>), grid, kBlock, d, int(r));
-    } else if (d.crec[0] && c->vote_satkey) {
-      LAUNCH(2, r, (mm_vote_lane<kBlock, false, 0, true, false, true>), grid, kBlock, d, int(r));
-    } else if (d.crec[0]) {
-      LAUNCH(2, r, (mm_vote_lane<kBlock, false, 0, true>), grid, kBlock, d, int(r));
-    } else {
-      LAUNCH(2, r, (mm_vote_lane<kBlock, false>), grid, kBlock, d, int(r));
-    }
-    break;
-  case 16:
-    LAUNCH(2, r, mm_vote<16>, grid, kBlock, d, int(r));
-    break;
-  case 32:
-    LAUNCH(2, r, mm_vote<32>, grid, kBlock, d, int(r));
-    break;
-  default:
-    LAUNCH(2, r, mm_vote<64>, grid, kBlock, d, int(r));
-    break;
-  }
-  return 0;
-}
+// The round engine's kernels by mode.  Vote: rows 0-2 the short-row lane vote (no row records / row records / row
+// records + ready queue; groups of 4 and 8: one lane per row, more gathers in flight per wave), each [without, with] the
+// sat-key filter, in its LDS-bitmap form and its scan form; rows 3-5 the long-row votes mm_vote<16|32|64> (scan only).
+struct VoteKernels {
+  VoteKernel bitmap, scan;
+};
+constexpr VoteKernels kVoteTable[6][2] = {
+    {{mm_vote_lane<kVBlock, true>, mm_vote_lane<kBlock, false>}, {mm_vote_lane<kVBlock, true>, mm_vote_lane<kBlock, false>}},
+    {{mm_vote_lane<kVBlock, true, 0, true>, mm_vote_lane<kBlock, false, 0, true>},
+     {mm_vote_lane<kVBlock, true, 0, true, false, true>, mm_vote_lane<kBlock, false, 0, true, false, true>}},
+    {{mm_vote_lane<kVBlock, true, 0, true, true>, mm_vote_lane<kBlock, false, 0, true, true>},
+     {mm_vote_lane<kVBlock, true, 0, true, true, true>, mm_vote_lane<kBlock, false, 0, true, true, true>}},
+    {{nullptr, mm_vote<16>}, {nullptr, mm_vote<16>}},
+    {{nullptr, mm_vote<32>}, {nullptr, mm_vote<32>}},
+    {{nullptr, mm_vote<64>}, {nullptr, mm_vote<64>}}};
+// Saturation: [mm_ready's list, the ready queue][1, 2, 4 waves per ready constraint]
+constexpr SatKernel kSatTable[2][3] = {{mm_saturate<1>, mm_saturate<2>, mm_saturate<4>},
+                                       {mm_saturate_q<1>, mm_saturate_q<2>, mm_saturate_q<4>}};
+constexpr UpdKernel kUpdTable[2] = {mm_update<false>, mm_update<true>};
 
-// Slots: 0 mm_init_cnsts, 1 mm_init_vars, 2 mm_vote, 3 mm_ready, 4 mm_saturate, 5 mm_update,
-// 6 compaction.
-int solve_maxmin(lmmhip_ctx* c, double prec) {
-  c->ran_engine = LMMHIP_RAN_ROUNDS;
-  Dev& d = c->d;
-  struct RowofOff {  // the other engines never see the row map / row records (their compactions do not
-    Dev& d;          // maintain them)
-    ~RowofOff() {
-      d.crec[0] = d.crec[1] = d.crec[2] = nullptr;
-      d.rdq[0] = d.rdq[1] = nullptr;
-      d.rqst = d.useg = d.ucnt = nullptr;
-    }
-  } rowof_off{d};
+static RoundPlan round_plan(const lmmhip_ctx* c, const Dev& d) {
+  RoundPlan P;
+  const bool short_rows = c->group == 4 || c->group == 8;
   // packed row records for the re-votes (vote_row: the row's variable and CSR range from one 8-B record and
   // its successor instead of the cvar / crow arrays, one line per re-vote less): C2 25.94-26.00 vs 26.10-26.17
   // ms, stress 28.83 vs 29.13 (same box).  LMMHIP_CREC=0: off.
-  d.crec[0] = d.crec[1] = d.crec[2] = nullptr;
-  if ((c->group == 4 || c->group == 8) && env_int("LMMHIP_CREC", 1)) {
-    for (int k = 0; k < 3; k++) {
-      uint2* p = nullptr;
-      if (int rc = scratch(c, c->rounds.crec[k], int64_t(d.nV) + 1, &p))
-        return rc;
-      d.crec[k] = p;
-    }
-  }
+  P.crec = short_rows && env_int("LMMHIP_CREC", 1);
+  // Launch-width caps (tuning knobs, environment; 0 = uncapped): fewer blocks cut the fixed per-round
+  // cost of the grid-stride round kernels once the alive set is small.
+  const int cap_upd = env_int("LMMHIP_UPD_BLOCKS", 0);
+  // the saturation's grid capped at 4 workgroups per CU (round 5, same box: C2 24.73-24.90 ms against 25.04-25.16
+  // uncapped, i.e. up to kMaxBlocks = 2048; 768: 24.79-25.03, 1280: 24.76-24.81, 1536: 24.83-25.00, 512: 25.42-25.73;
+  // stress 27.99-28.05 vs 28.29-28.36): every workgroup first rebuilds the prefix of the update's segment counts,
+  // and half as many of them still give each ready constraint its waves
+  // (with 4 update workgroups per CU: 5 per CU, 24.41-24.45 ms against 24.52-24.54 at 4 and 24.52-24.60 at 6 / 8)
+  P.cap_sat = env_int("LMMHIP_SAT_BLOCKS", 5 * c->n_cu);
   // ready constraints without the mm_ready pass: the update's workgroups (at most kMaxBlocks, each updating
   // at most kUSeg constraints) list them for the next round, the vote queues the ones it makes ready (C2
   // 25.07-25.22 vs 25.34-25.39 ms, stress 28.29 vs 28.46, same box; LMMHIP_RDQ=0: the mm_ready pass)
-  d.rdq[0] = d.rdq[1] = nullptr;
-  d.rqst = d.useg = d.ucnt = nullptr;
   // (<= kMaxBlocks) Update workgroups: 4 per CU, each with a longer segment, so that the saturation's prefix over
   // the segment counts is shorter — but enough of them to keep every segment within kUSeg (LMMHIP_UPDQ_BLOCKS).
   // Round 5, same box: C2 24.52-24.54 ms against 24.84-24.85 with one per 256 constraints (2,048 at C2), stress
@@ -138,72 +131,46 @@ int solve_maxmin(lmmhip_ctx* c, double prec) {
   const int64_t gU_rdq = std::max<int64_t>(1, std::min<int64_t>(grid_for(d.nC, kBlock),
       std::max<int64_t>(gU_need, env_int("LMMHIP_UPDQ_BLOCKS", 4 * c->n_cu))));
   const int64_t per_blk = int64_t(kBlock) * ((int64_t(d.nC) + gU_rdq * kBlock - 1) / (gU_rdq * kBlock));
-  if (d.crec[0] && env_int("LMMHIP_RDQ", 1) && per_blk <= kUSeg && env_int("LMMHIP_UPD_BLOCKS", c->tune_upd) == 0) {
-    int32_t *q0 = nullptr, *q1 = nullptr, *st = nullptr, *sg = nullptr, *uc = nullptr;
-    const int64_t n = std::max<int64_t>(d.nC, 1);
-    if (int rc = scratch(c, c->rounds.rdq[0], n, &q0) | scratch(c, c->rounds.rdq[1], n, &q1) |
-                 scratch(c, c->rounds.rqst, n, &st) | scratch(c, c->rounds.useg, gU_rdq * kUSeg, &sg) |
-                 scratch(c, c->rounds.ucnt, kMaxBlocks, &uc))
-      return rc;
-    HIPCHK(hipMemsetAsync(st, 0xFF, size_t(n) * sizeof(int32_t), c->stream));
-    HIPCHK(hipMemsetAsync(uc, 0, size_t(kMaxBlocks) * sizeof(int32_t), c->stream));
-    d.rdq[0] = q0;
-    d.rdq[1] = q1;
-    d.rqst = st;
-    d.useg = sg;
-    d.ucnt = uc;
-  }
+  P.rdq = P.crec && env_int("LMMHIP_RDQ", 1) && per_blk <= kUSeg && cap_upd == 0;
   // the filter retires the rows of saturated targets on the key it gathered (kSatKey, vote_waves) and the re-votes read
   // no variable state (the row-record forms of the short-row vote).  LMMHIP_SATKEY=0: the state-read path
-  c->vote_satkey = env_int("LMMHIP_SATKEY", 1) != 0;
-  c->vote_bits = env_int("LMMHIP_VOTE_BITS", 1) != 0;
-  c->vote_bits_rows = env_int("LMMHIP_VOTE_BITS_ROWS", 0);
-  const int gC4 = grid_for(d.nC, kBlock / kWave);
-  const int gC = grid_for(d.nC, kBlock);
-  LAUNCH(0, -1, mm_init_cnsts, gC4, kBlock, d, prec);
-  LAUNCH(1, -1, mm_init_vars, grid_for(d.nV, kBlock), kBlock, d);
-  LAUNCH(1, -1, mm_clist, std::min(gC, 2 * c->n_cu), kBlock, d, 1);
-  HIPCHK(hipMemsetAsync(d.chgbits, 0, sizeof(uint64_t) * ((d.nC + 127) / 128 * 2 + 2), c->stream));
-  // Launch-width caps (tuning knobs, environment; 0 = uncapped): fewer blocks cut the fixed per-round
-  // cost of the grid-stride round kernels once the alive set is small.
-  const int cap_upd = env_int("LMMHIP_UPD_BLOCKS", c->tune_upd);
-  // the saturation's grid capped at 4 workgroups per CU (round 5, same box: C2 24.73-24.90 ms against 25.04-25.16
-  // uncapped, i.e. up to kMaxBlocks = 2048; 768: 24.79-25.03, 1280: 24.76-24.81, 1536: 24.83-25.00, 512: 25.42-25.73;
-  // stress 27.99-28.05 vs 28.29-28.36): every workgroup first rebuilds the prefix of the update's segment counts,
-  // and half as many of them still give each ready constraint its waves
-  // (with 4 update workgroups per CU: 5 per CU, 24.41-24.45 ms against 24.52-24.54 at 4 and 24.52-24.60 at 6 / 8)
-  const int cap_sat = env_int("LMMHIP_SAT_BLOCKS", c->tune_sat > 0 ? c->tune_sat : 5 * c->n_cu);
-  auto capped = [](int g, int cap) { return cap > 0 && g > cap ? cap : g; };
-  const int gU = capped(gC, cap_upd);  // mm_update: thread per constraint, identity order
-  const int gUq = int(gU_rdq);          // (ready-queue mode: at most kUSeg constraints per workgroup)
+  P.satkey = env_int("LMMHIP_SATKEY", 1) != 0;
+  const int row = short_rows ? (P.rdq ? 2 : P.crec ? 1 : 0) : c->group == 16 ? 3 : c->group == 32 ? 4 : 5;
+  const VoteKernels& vk = kVoteTable[row][P.satkey];
+  // the LDS bitmap of changed constraints (one 1024-thread workgroup per CU); below LMMHIP_VOTE_BITS_ROWS alive rows
+  // (host view, A/B knob; 0 = always) the change stamps gathered per row instead: no ~125-KB copy per CU
+  // (LMMHIP_VOTE_BITS=0: always the stamps' path)
+  const bool bits = int64_t(d.nC) <= int64_t(kBitWords) * 64 && env_int("LMMHIP_VOTE_BITS", 1) != 0;
+  P.vote_bitmap = bits ? vk.bitmap : nullptr;
+  P.vote_scan = vk.scan;
+  P.vote_bits_rows = env_int("LMMHIP_VOTE_BITS_ROWS", 0);
   // mm_saturate: waves per ready constraint and the grid's block cap (measurement knobs)
   const int sat_k = env_int("LMMHIP_SAT_WAVES", c->sat_waves);
-  const int sat_max = env_int("LMMHIP_SAT_GRID_MAX", kMaxBlocks);
-  auto sat_grid = [&](int64_t n) { return int(std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, sat_max))); };
+  P.sat_waves = sat_k == 1 || sat_k == 2 ? sat_k : 4;
+  P.saturate = kSatTable[P.rdq][P.sat_waves == 4 ? 2 : P.sat_waves - 1];
+  P.sat_max = env_int("LMMHIP_SAT_GRID_MAX", kMaxBlocks);
+  P.update = kUpdTable[P.rdq];
+  P.g_init_c = grid_for(d.nC, kBlock / kWave);
+  P.g_c = grid_for(d.nC, kBlock);
+  // mm_update: thread per constraint, identity order (ready-queue mode: at most kUSeg constraints per workgroup)
+  P.g_upd = P.rdq ? int(gU_rdq) : cap_upd > 0 && P.g_c > cap_upd ? cap_upd : P.g_c;
   // Compaction cadence (knobs): alive rows are re-counted every cmp_every rounds and rewritten when
   // fewer than cmp_pct % of the scanned rows are alive; the alive-constraint list every cl_every rounds.
   // Both decide and switch buffers on the device (ctl CTL_BUF / CTL_CB): no host round trip.
   // (round 5, re-swept on the final code, same box: every 48 rounds 24.94-25.08 ms against 25.10-25.21 at 32, 25.49-25.56
   // at 16, 25.11-25.21 at 64, 25.30-25.34 at 96; stress 28.29-28.37 vs 28.42-28.44)
-  const int cmp_every = env_int("LMMHIP_COMPACT_EVERY", 48);
-  const int cmp_pct = env_int("LMMHIP_COMPACT_PCT", 75);
-  const int cl_every = env_int("LMMHIP_CLIST_EVERY", 8);
-  // Every round fixes at least one variable (DESIGN.md §3, progress), so nV + 2 rounds bound it.
-  const int64_t max_rounds = int64_t(d.nV) + 2;
-  // Host view of the sizes (upper bounds: rows and constraints only leave), refreshed at every poll; they
-  // size grids only, the kernels read the exact counts from the control words.
-  int64_t r = 0, last_compact = 0, last_clist = 0, nrows = d.nV, ncl = d.nC;
-  // Termination polls are pipelined (CtlPoll): a chunk queued after the last round is a run of launches that
-  // return at once (CTL_DONE).
-  int chunk = 2;
+  P.cmp_every = env_int("LMMHIP_COMPACT_EVERY", 48);
+  P.cmp_pct = env_int("LMMHIP_COMPACT_PCT", 75);
+  P.cl_every = env_int("LMMHIP_CLIST_EVERY", 8);
   // rounds queued per poll: the host learns of termination one chunk late, so up to 2 x chunk_max no-op
   // rounds run after the last one (LMMHIP_CHUNK_MAX, A/B knob): C2 25.96-25.99 ms at 16, 26.01 at 8,
   // 26.15-26.20 at 4; round 5, with compactions every 48 rounds: 25.03-25.06 at 32 against 25.07-25.08 at 16
-  const int64_t hint = env_int("LMMHIP_ROUND_HINT", 1) ? c->hint_rounds_mm : 0;  // (round_hint_chunk)
+  P.chunk.hint = env_int("LMMHIP_ROUND_HINT", 1) ? c->hint_rounds_mm : 0;  // (round_hint_chunk)
   // under a hint no returning rounds follow the last one, and 64-round chunks (fewer polls, a sparser list / compaction
   // cadence) measured 23.13-23.36 ms against 23.21-23.47 at 32 over five same-box pairs, stress 26.85 vs 26.88
   // (scripts/gpu_r06_v.sh, _w.sh)
-  const int chunk_max = std::max(2, env_int("LMMHIP_CHUNK_MAX", hint > 0 ? 64 : 32));
+  P.chunk.first = 2;
+  P.chunk.max = std::max(2, env_int("LMMHIP_CHUNK_MAX", P.chunk.hint > 0 ? 64 : 32));
   // Near the end of the solve, short chunks: the rounds queued after the last one are no-op launches of the full
   // grids (~32 of them after C2's last round with 32-round chunks, rocprofv3 trace of round 5), so once the alive rows
   // (host view: refreshed at each compaction) fall to LMMHIP_CHUNK_TAIL_PCT % of the variables (default 5), or below
@@ -211,47 +178,90 @@ int solve_maxmin(lmmhip_ctx* c, double prec) {
   // LMMHIP_CHUNK_TAIL rounds (default 4).  Round 5, same box, two passes (scripts/gpu_r05_ctail.sh,
   // profiles/r05_ab_c2_ctail.json): C2 23.90-23.95 ms at 5e5 rows (5 %) / 4 rounds against 24.10-24.12 without;
   // 1e6 / 8 and 2e6 / 8 23.92-23.94, 1e6 / 4 23.95-24.07; the constraint-list thresholds (2e4, 1e5) 24.06-24.11.
-  const int64_t ctail_rows = env_int("LMMHIP_CHUNK_TAIL_ROWS",
-                                     int(int64_t(d.nV) * std::max(0, env_int("LMMHIP_CHUNK_TAIL_PCT", 5)) / 100));
-  const int64_t ctail_cnst = env_int("LMMHIP_CHUNK_TAIL_CNST", 0);
-  const int ctail = std::max(1, env_int("LMMHIP_CHUNK_TAIL", 4));
-  auto round_launches = [&](int64_t r) -> int {
-    if (int rc = launch_vote(c, r, nrows))
+  // (the short tail chunks stay under a hint too: dropping them measured 23.10 against 23.05-23.08 ms,
+  // scripts/gpu_r06_t.sh)
+  P.tail_rows = env_int("LMMHIP_CHUNK_TAIL_ROWS",
+                        int(int64_t(d.nV) * std::max(0, env_int("LMMHIP_CHUNK_TAIL_PCT", 5)) / 100));
+  P.tail_cnst = env_int("LMMHIP_CHUNK_TAIL_CNST", 0);
+  P.chunk.tail = std::max(1, env_int("LMMHIP_CHUNK_TAIL", 4));
+  return P;
+}
+
+// The plan's buffers, into the solve's own Dev: the context's never carries them (lmm_dev.hpp), so no other engine —
+// whose compactions do not maintain the row records — ever sees them.
+static int round_buffers(lmmhip_ctx* c, Dev& d, const RoundPlan& P) {
+  if (P.crec)
+    for (int k = 0; k < 3; k++)
+      if (int rc = scratch(c, c->rounds.crec[k], int64_t(d.nV) + 1, &d.crec[k]))
+        return rc;
+  if (P.rdq) {
+    const int64_t n = std::max<int64_t>(d.nC, 1);
+    if (int rc = scratch(c, c->rounds.rdq[0], n, &d.rdq[0]) | scratch(c, c->rounds.rdq[1], n, &d.rdq[1]) |
+                 scratch(c, c->rounds.rqst, n, &d.rqst) | scratch(c, c->rounds.useg, int64_t(P.g_upd) * kUSeg, &d.useg) |
+                 scratch(c, c->rounds.ucnt, kMaxBlocks, &d.ucnt))
       return rc;
-    if (d.rdq[0]) {  // no mm_ready pass: the update's segments (gUq workgroups) and the vote's queue
-      if (sat_k == 1)
-        LAUNCH(4, r, mm_saturate_q<1>, capped(sat_grid(ncl), cap_sat), kBlock, d, int(r), gUq);
-      else if (sat_k == 2)
-        LAUNCH(4, r, mm_saturate_q<2>, capped(sat_grid(2 * ncl), cap_sat), kBlock, d, int(r), gUq);
-      else
-        LAUNCH(4, r, mm_saturate_q<4>, capped(sat_grid(4 * ncl), cap_sat), kBlock, d, int(r), gUq);
-      LAUNCH(5, r, mm_update<true>, gUq, kBlock, d, int(r), prec);
-      return 0;
-    }
+    HIPCHK(hipMemsetAsync(d.rqst, 0xFF, size_t(n) * sizeof(int32_t), c->stream));
+    HIPCHK(hipMemsetAsync(d.ucnt, 0, size_t(kMaxBlocks) * sizeof(int32_t), c->stream));
+  }
+  return 0;
+}
+
+// The alive-row buffer in use is read by the vote on the device (ctl CTL_BUF); nrows (an upper bound of its
+// rows, refreshed at every poll) only sizes the scan forms' grids (one lane per row in the work-queue scan).
+static int launch_vote(lmmhip_ctx* c, const Dev& d, const RoundPlan& P, int64_t r, int64_t nrows) {
+  const bool bitmap = P.vote_bitmap && nrows >= P.vote_bits_rows;
+  if (bitmap && c->profiling && c->vote_diag) {  // measurement: bitmap load alone, filter alone (slot 7)
+    LAUNCH(7, r + 1000000, (mm_vote_lane<kVBlock, true, 2>), c->n_cu, kVBlock, d, int(r));
+    LAUNCH(7, r, (mm_vote_lane<kVBlock, true, 1>), c->n_cu, kVBlock, d, int(r));
+    LAUNCH(7, r, mm_vote_diagcount, grid_for((int64_t(d.nC) + 63) / 64, kBlock), kBlock, d, int(r));
+  }
+  LAUNCH(2, r, bitmap ? P.vote_bitmap : P.vote_scan, bitmap ? c->n_cu : grid_for(nrows, kBlock), bitmap ? kVBlock : kBlock,
+         d, int(r));
+  return 0;
+}
+
+// Slots: 0 mm_init_cnsts, 1 mm_init_vars, 2 mm_vote, 3 mm_ready, 4 mm_saturate, 5 mm_update,
+// 6 compaction.
+int solve_maxmin(lmmhip_ctx* c, double prec) {
+  c->ran_engine = LMMHIP_RAN_ROUNDS;
+  Dev d = c->d;  // (a copy, as in the other engines: the mode's buffers go into it alone)
+  const RoundPlan P = round_plan(c, d);
+  if (int rc = round_buffers(c, d, P))
+    return rc;
+  LAUNCH(0, -1, mm_init_cnsts, P.g_init_c, kBlock, d, prec);
+  LAUNCH(1, -1, mm_init_vars, grid_for(d.nV, kBlock), kBlock, d);
+  LAUNCH(1, -1, mm_clist, std::min(P.g_c, 2 * c->n_cu), kBlock, d, 1);
+  HIPCHK(hipMemsetAsync(d.chgbits, 0, sizeof(uint64_t) * ((d.nC + 127) / 128 * 2 + 2), c->stream));
+  // Host view of the sizes (upper bounds: rows and constraints only leave), refreshed at every poll; they
+  // size grids only, the kernels read the exact counts from the control words.
+  int64_t last_compact = 0, last_clist = 0, nrows = d.nV, ncl = d.nC;
+  auto round_launches = [&](int64_t r) -> int {
+    if (int rc = launch_vote(c, d, P, r, nrows))
+      return rc;
     const int gL = grid_for(ncl, kBlock);
-    LAUNCH(3, r, mm_ready, gL, kBlock, d);
-    if (sat_k == 1)
-      LAUNCH(4, r, mm_saturate<1>, capped(sat_grid(ncl), cap_sat), kBlock, d, int(r), gL);
-    else if (sat_k == 2)
-      LAUNCH(4, r, mm_saturate<2>, capped(sat_grid(2 * ncl), cap_sat), kBlock, d, int(r), gL);
-    else
-      LAUNCH(4, r, mm_saturate<4>, capped(sat_grid(4 * ncl), cap_sat), kBlock, d, int(r), gL);
-    LAUNCH(5, r, mm_update<false>, gU, kBlock, d, int(r), prec);
+    if (!P.rdq)  // (ready-queue mode: no mm_ready pass, the update's segments — g_upd of them — and the vote's queue)
+      LAUNCH(3, r, mm_ready, gL, kBlock, d);
+    const int64_t gS = std::max<int64_t>(1, std::min<int64_t>((P.sat_waves * ncl + kBlock - 1) / kBlock, P.sat_max));
+    LAUNCH(4, r, P.saturate, int(P.cap_sat > 0 && gS > P.cap_sat ? P.cap_sat : gS), kBlock, d, int(r),
+           P.rdq ? P.g_upd : gL);
+    LAUNCH(5, r, P.update, P.g_upd, kBlock, d, int(r), prec);
     return 0;
   };
-  // the alive-constraint list and the alive-row compaction at the end of a chunk (their cadence is the chunks')
+  // the termination test, then the alive-constraint list and the alive-row compaction, at the end of a chunk (their
+  // cadence is the chunks')
   auto chunk_end = [&](int64_t r) -> int {
+    LAUNCH(6, r, mm_done, 1, kBlock, d, P.g_upd);
     const int gL = grid_for(ncl, kBlock);
     bool cl = false, cm = false;
-    if (r - last_clist >= cl_every && ncl > 4096) {  // alive-constraint list (order not preserved)
+    if (r - last_clist >= P.cl_every && ncl > 4096) {  // alive-constraint list (order not preserved)
       LAUNCH(6, r, mm_clist, std::min(gL, 2 * c->n_cu), kBlock, d, 0);
       last_clist = r;
       cl = true;
     }
-    if (r - last_compact >= cmp_every && nrows > 4096) {  // order-preserving compaction of the alive rows
+    if (r - last_compact >= P.cmp_every && nrows > 4096) {  // order-preserving compaction of the alive rows
       const int nblk = int((nrows + kCompactRows - 1) / kCompactRows);
       LAUNCH(6, r, cmp_count, nblk, kBlock, d);
-      LAUNCH(6, r, cmp_scan, 1, 1024, d, nblk, cmp_pct);
+      LAUNCH(6, r, cmp_scan, 1, 1024, d, nblk, P.cmp_pct);
       LAUNCH(6, r, cmp_write, nblk, kBlock, d);
       last_compact = r;
       cm = true;
@@ -260,43 +270,58 @@ int solve_maxmin(lmmhip_ctx* c, double prec) {
       LAUNCH(6, r, mm_flip, 1, 1, d, int(cl), int(cm));
     return 0;
   };
-  CtlPoll poll;
-  if (int rc = poll.init(c))
-    return rc;
-  for (;;) {
-    bool stop = false;
-    const int n = round_hint_chunk(r, chunk, hint, &stop);
-    for (int k = 0; k < n; k++, r++)
-      if (int rc = round_launches(r))
-        return rc;
-    LAUNCH(6, r, mm_done, 1, kBlock, d, d.rdq[0] ? gUq : gU);
-    if (int rc = chunk_end(r))
-      return rc;
-    const int32_t* h = nullptr;
-    if (int rc = poll.step(d, r, stop, &h))
-      return rc;
+  auto in_tail = [&](const int32_t* h) {
     if (h) {
-      if (h[CTL_DONE])
-        break;
       ncl = h[CTL_NCL0 + h[CTL_CB]];
       nrows = h[CTL_NROWS + h[CTL_BUF]];
     }
-    // the guard counts the rounds the device has RUN without finishing (CTL_ROUNDS of the newest words), not the rounds
-    // queued: the polls are one chunk behind, so a system of 3 variables and 3 rounds has 6 rounds queued when the
-    // words of its first two arrive, and counting those failed it
-    if (h && h[CTL_ROUNDS] > max_rounds)
-      return fail(LMMHIP_E_NOCONVERGE, "maxmin round guard tripped");
-    if (chunk < chunk_max)
-      chunk = std::min(2 * chunk, chunk_max);
-    // (the short tail chunks stay under a hint too: dropping them measured 23.10 against 23.05-23.08 ms,
-    // scripts/gpu_r06_t.sh)
-    if ((nrows <= ctail_rows || ncl <= ctail_cnst) && chunk > ctail)
-      chunk = ctail;
-  }
-  if (int rc = poll_ctl(c))  // (the queued tail has run: final words for the stats)
+    return nrows <= P.tail_rows || ncl <= P.tail_cnst;
+  };
+  if (int rc = run_chunks(c, d, P.chunk, round_launches, chunk_end, in_tail))
     return rc;
   c->hint_rounds_mm = int64_t(c->h_ctl.p[CTL_LASTR]) + 1;
   return 0;
+}
+
+static FrontierPlan frontier_plan(const lmmhip_ctx* c, const Dev& d) {
+  FrontierPlan P;
+  // fr_update / fr_vote (/ fr_sat<256>) workgroups; one for a system without constraints (every variable disabled
+  // or on zero-bound constraints only: nothing flattened), whose first round then finds nothing alive — a grid of
+  // zero workgroups is a launch error
+  P.nblk = int(std::max<int64_t>(1, (int64_t(d.nC) + kFB - 1) / kFB));
+  P.nblk_sat = int(std::max<int64_t>(1, (int64_t(d.nC) + kFS - 1) / kFS));  // fr_sat workgroups
+  // constraints of more CSC chunks than this saturate in fr_sat_big, kFrBigWaves waves each over the whole grid
+  // (LMMHIP_FR_BIGCH, A/B knob: fat-tree core links' chunk chains in C4)
+  P.bigch = std::max(1, env_int("LMMHIP_FR_BIGCH", kFrBigCh));
+  P.big = c->frontier.maxdeg > P.bigch * kWave;
+  P.bigw = std::max(1, env_int("LMMHIP_FR_BIGW", kFrBigWaves));  // waves per big constraint (A/B knob)
+  P.g_big = std::min(kMaxBlocks, 4 * c->n_cu);
+  // (round 6, removed after their A/Bs: the re-vote reading the floors with the keys, LMMHIP_FR_MFEARLY, and the round
+  // engine's chunk body in fr_sat, LMMHIP_FR_SATOLD — both slower on C2 and C4, scripts/gpu_fr_ab.sh)
+  // re-votes keep 16 row elements in registers when the mean row is longer than 8 (LMMHIP_FR_R16=0: 8)
+  P.long_rows = c->group > 8 && env_int("LMMHIP_FR_R16", 1) != 0;
+  // fr_vote: segments per workgroup, so that the grid still covers the chip twice (C2: 4, small systems: 1)
+  P.spb = int(std::max<int64_t>(1, std::min<int64_t>(kFVS, int64_t(P.nblk) / (2 * int64_t(c->n_cu)))));
+  // fr_sat workgroup: kFS threads (the round-4 choice on C2-size systems) unless that leaves the chip mostly
+  // idle — C4 (25 workgroups of kFS): 3.37-3.40 ms with 256-thread workgroups against 3.49
+  const int sat_b0 = int64_t(P.nblk_sat) >= 2 * int64_t(c->n_cu) ? kFS : 256;
+  P.sat_b = env_int("LMMHIP_FR_SATB", sat_b0) == 256 ? 256 : kFS;
+  // fr_update: every constraint's state loaded with its key (one dependent level less) on the small systems, where the
+  // 256-thread saturation workgroups run (LMMHIP_FR_UPDSPEC, A/B knob)
+  P.upd_spec = env_int("LMMHIP_FR_UPDSPEC", P.sat_b == 256 ? 1 : 0);
+  // rounds queued per poll: the host learns of termination one chunk late, so up to 2 x chunk_max no-op
+  // rounds run after the last one (LMMHIP_CHUNK_MAX, A/B knob): C4 3.48 ms at 8, 3.51-3.53 at 4, 3.55 at 16
+  // (short rounds: the no-op tail is a larger share)
+  const int chunk_max = std::max(2, env_int("LMMHIP_CHUNK_MAX", 8));
+  P.chunk.hint = env_int("LMMHIP_ROUND_HINT", 1) ? c->hint_rounds_fr : 0;
+  // with a hint the returning rounds after the last one are gone, and what longer chunks cost is with them: fewer
+  // polls (mm_ctl_out, 3.6 us of kernel each) up to the hinted end (LMMHIP_HINT_CHUNK_MAX, A/B knob)
+  P.chunk.max = P.chunk.hint > 0 ? std::max(chunk_max, env_int("LMMHIP_HINT_CHUNK_MAX", 32)) : chunk_max;
+  // and the first chunk need not be short either (its point is an early poll for systems of few rounds)
+  P.chunk.first = 2;
+  if (P.chunk.hint > 0)
+    P.chunk.first = std::max(2, std::min(P.chunk.max, env_int("LMMHIP_HINT_CHUNK0", P.chunk.max)));
+  return P;
 }
 
 // Frontier engine (lmm_frontier_kernels.hpp): three launches per round, work proportional to the touched
@@ -308,11 +333,7 @@ int solve_maxmin_frontier(lmmhip_ctx* c, double prec) {
   if (!c->vote_diag)  // per-round diagnostic counters only on request (LMMHIP_VOTE_DIAG): they cost atomics
     d.vstat = nullptr;
   const int64_t nnz = std::max<int64_t>(d.nnz, 1);
-  // fr_update / fr_vote (/ fr_sat<256>) workgroups; one for a system without constraints (every variable disabled
-  // or on zero-bound constraints only: nothing flattened), whose first round then finds nothing alive — a grid of
-  // zero workgroups is a launch error
-  const int nblk = int(std::max<int64_t>(1, (int64_t(d.nC) + kFB - 1) / kFB));
-  const int nblkS = int(std::max<int64_t>(1, (int64_t(d.nC) + kFS - 1) / kFS));  // fr_sat workgroups
+  const int64_t nblk = std::max<int64_t>(1, (int64_t(d.nC) + kFB - 1) / kFB);  // (FrontierPlan::nblk)
   int2* cs = nullptr;
   int32_t* md = nullptr;
   int rc = scratch(c, c->frontier.c2s, nnz, &cs);
@@ -322,7 +343,7 @@ int solve_maxmin_frontier(lmmhip_ctx* c, double prec) {
   rc = rc ? rc : scratch(c, c->frontier.key, std::max<int64_t>(d.nC, 1), &d.key32);
   rc = rc ? rc : scratch(c, c->frontier.qa, nnz, &d.fq_a);
   rc = rc ? rc : scratch(c, c->frontier.qb, nnz, &d.fq_b);
-  rc = rc ? rc : scratch(c, c->frontier.qn, int64_t(nblk) + 1, &d.fq_n);
+  rc = rc ? rc : scratch(c, c->frontier.qn, nblk + 1, &d.fq_n);
   rc = rc ? rc : scratch(c, c->frontier.md, 1, &md);
   if (rc)
     return rc;
@@ -337,84 +358,33 @@ int solve_maxmin_frontier(lmmhip_ctx* c, double prec) {
     HIPCHK(hipStreamSynchronize(c->stream));
     c->frontier.map_ok = true;
   }
-  // constraints of more CSC chunks than this saturate in fr_sat_big, kFrBigWaves waves each over the whole grid
-  // (LMMHIP_FR_BIGCH, A/B knob: fat-tree core links' chunk chains in C4)
-  const int bigch = std::max(1, env_int("LMMHIP_FR_BIGCH", kFrBigCh));
-  const bool big = c->frontier.maxdeg > bigch * kWave;
-  const int bigw = std::max(1, env_int("LMMHIP_FR_BIGW", kFrBigWaves));  // waves per big constraint (A/B knob)
-  // (round 6, removed after their A/Bs: the re-vote reading the floors with the keys, LMMHIP_FR_MFEARLY, and the round
-  // engine's chunk body in fr_sat, LMMHIP_FR_SATOLD — both slower on C2 and C4, scripts/gpu_fr_ab.sh)
-  // re-votes keep 16 row elements in registers when the mean row is longer than 8 (LMMHIP_FR_R16=0: 8)
-  const bool long_rows = c->group > 8 && env_int("LMMHIP_FR_R16", 1) != 0;
-  // fr_vote: segments per workgroup, so that the grid still covers the chip twice (C2: 4, small systems: 1)
-  const int spb = int(std::max<int64_t>(1, std::min<int64_t>(kFVS, int64_t(nblk) / (2 * int64_t(c->n_cu)))));
-  // fr_sat workgroup: kFS threads (the round-4 choice on C2-size systems) unless that leaves the chip mostly
-  // idle — C4 (25 workgroups of kFS): 3.37-3.40 ms with 256-thread workgroups against 3.49
-  const int sat_b0 = int64_t(nblkS) >= 2 * int64_t(c->n_cu) ? kFS : 256;
-  const int sat_b = env_int("LMMHIP_FR_SATB", sat_b0) == 256 ? 256 : kFS;
-  // fr_update: every constraint's state loaded with its key (one dependent level less) on the small systems, where the
-  // 256-thread saturation workgroups run (LMMHIP_FR_UPDSPEC, A/B knob)
-  const int upd_spec = env_int("LMMHIP_FR_UPDSPEC", sat_b == 256 ? 1 : 0);
-  const int gC4 = grid_for(d.nC, kBlock / kWave);
-  LAUNCH(0, -1, mm_init_cnsts, gC4, kBlock, d, prec);
+  const FrontierPlan P = frontier_plan(c, d);
+  LAUNCH(0, -1, mm_init_cnsts, grid_for(d.nC, kBlock / kWave), kBlock, d, prec);
   LAUNCH(1, -1, fr_init_vars, grid_for(std::max<int64_t>(std::max<int64_t>(d.nV, d.nC), d.nnz / 4), kBlock), kBlock, d);
-  const int64_t max_rounds = int64_t(d.nV) + 2;  // every round fixes a variable (progress)
-  const int gbig = std::min(kMaxBlocks, 4 * c->n_cu);
   auto round_launches = [&](int64_t r) -> int {
     if (r == 0) {
       LAUNCH(2, r, fr_vote_all, grid_for(d.nV, kBlock), kBlock, d);
       LAUNCH(2, r, fr_minfl_all, grid_for(d.nC, kBlock / 16), kBlock, d);
-    } else if (long_rows) {  // (LV08 routes: ~12 elements per row)
-      LAUNCH(2, r, fr_vote<16>, (nblk + spb - 1) / spb, kFB, d, int(r), spb);
+    } else if (P.long_rows) {  // (LV08 routes: ~12 elements per row)
+      LAUNCH(2, r, fr_vote<16>, (P.nblk + P.spb - 1) / P.spb, kFB, d, int(r), P.spb);
     } else {
-      LAUNCH(2, r, fr_vote<8>, (nblk + spb - 1) / spb, kFB, d, int(r), spb);
+      LAUNCH(2, r, fr_vote<8>, (P.nblk + P.spb - 1) / P.spb, kFB, d, int(r), P.spb);
     }
-    if (sat_b == 256)
-      LAUNCH(4, r, fr_sat<256>, nblk, 256, d, int(r), bigch);
+    if (P.sat_b == 256)
+      LAUNCH(4, r, fr_sat<256>, P.nblk, 256, d, int(r), P.bigch);
     else
-      LAUNCH(4, r, fr_sat<kFS>, nblkS, kFS, d, int(r), bigch);
-    if (big)
-      LAUNCH(4, r, fr_sat_big, gbig, kBlock, d, int(r), bigw);
-    LAUNCH(5, r, fr_update, nblk, kFB, d, int(r), prec, upd_spec);
+      LAUNCH(4, r, fr_sat<kFS>, P.nblk_sat, kFS, d, int(r), P.bigch);
+    if (P.big)
+      LAUNCH(4, r, fr_sat_big, P.g_big, kBlock, d, int(r), P.bigw);
+    LAUNCH(5, r, fr_update, P.nblk, kFB, d, int(r), prec, P.upd_spec);
     return 0;
   };
-  int64_t r = 0;
-  // pipelined termination polls, as solve_maxmin (CtlPoll); rounds queued after the last one return at once.  (Round 6,
+  // pipelined termination polls (run_chunks); rounds queued after the last one return at once.  (Round 6,
   // measured and not kept: fr_vote storing "done" into a pinned host word itself, so that a poll is the event
   // alone without mm_ctl_out — C4 3.083-3.091 ms against 3.060-3.069, scripts/gpu_r06_p.sh; and the launches paced
   // by a per-round progress word, 2-5 rounds queued ahead — 3.17-3.28 against 3.12, scripts/gpu_r06_o.sh.)
-  int chunk = 2;
-  // rounds queued per poll: the host learns of termination one chunk late, so up to 2 x chunk_max no-op
-  // rounds run after the last one (LMMHIP_CHUNK_MAX, A/B knob): C4 3.48 ms at 8, 3.51-3.53 at 4, 3.55 at 16
-  // (short rounds: the no-op tail is a larger share)
-  const int chunk_max = std::max(2, env_int("LMMHIP_CHUNK_MAX", 8));
-  CtlPoll poll;
-  if (int rc = poll.init(c))
-    return rc;
-  const int64_t hint = env_int("LMMHIP_ROUND_HINT", 1) ? c->hint_rounds_fr : 0;
-  // with a hint the returning rounds after the last one are gone, and what longer chunks cost is with them: fewer
-  // polls (mm_ctl_out, 3.6 us of kernel each) up to the hinted end (LMMHIP_HINT_CHUNK_MAX, A/B knob)
-  const int chunk_cap = hint > 0 ? std::max(chunk_max, env_int("LMMHIP_HINT_CHUNK_MAX", 32)) : chunk_max;
-  // and the first chunk need not be short either (its point is an early poll for systems of few rounds)
-  if (hint > 0)
-    chunk = std::max(chunk, std::min(chunk_cap, env_int("LMMHIP_HINT_CHUNK0", chunk_cap)));
-  for (;;) {
-    bool stop = false;
-    const int n = round_hint_chunk(r, chunk, hint, &stop);
-    for (int k = 0; k < n; k++, r++)
-      if (int rc = round_launches(r))
-        return rc;
-    const int32_t* h = nullptr;
-    if (int rc = poll.step(d, r, stop, &h))
-      return rc;
-    if (h && h[CTL_DONE])
-      break;
-    if (h && h[CTL_ROUNDS] > max_rounds)  // (rounds run, not rounds queued: see solve_maxmin)
-      return fail(LMMHIP_E_NOCONVERGE, "maxmin round guard tripped");
-    if (chunk < chunk_cap)
-      chunk = std::min(2 * chunk, chunk_cap);
-  }
-  if (int rc = poll_ctl(c))
+  // Nothing at the end of a chunk but the poll, and no tail rule.
+  if (int rc = run_chunks(c, d, P.chunk, round_launches, [](int64_t) { return 0; }, [](const int32_t*) { return false; }))
     return rc;
   c->hint_rounds_fr = int64_t(c->h_ctl.p[CTL_ROUNDS]) + 1;
   return 0;

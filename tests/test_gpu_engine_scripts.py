@@ -17,6 +17,8 @@ high degree):
 import ctypes as ct
 import functools
 import itertools
+import json
+import os
 
 import numpy as np
 import pytest
@@ -164,6 +166,45 @@ def test_round_engine_variants_on_scripts(shape, variant, compact, monkeypatch):
     # 4 more launches are one whole row compaction (count, scan, write) and the switch of the buffers
     if large and compact:
         assert _launches(d.s)[6] >= base.launches6 + 4, (env, _launches(d.s)[6], base.launches6)
+
+
+# ---- the launch sequence of the two round-chain engines ----------------------------------------------------------------
+# (shape, engine, forced compactions): the small shapes are below the 4096 rows / constraints under which nothing
+# compacts, the L ones are the smallest above them; the frontier engine has no compaction knobs
+LAUNCH_CASES = [(sh, eng, False) for sh in ("R4", "R8", "R16", "R4L", "R8L") for eng in ("rounds", "frontier")]
+LAUNCH_CASES += [(sh, "rounds", True) for sh in ("R4L", "R8L")]
+LAUNCH_RECORD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "round_chain_launches.json")
+
+
+def launch_case_id(shape, engine, compact):
+    return f"{shape}-{engine}" + ("-compact" if compact else "")
+
+
+def launch_counts(shape, engine):
+    """kernel_launches (8 slots) of a first solve of the shape's script (seed 1) and of a second solve of the same
+    system on the same context, which chunks by the first one's round count (the hint)."""
+    d = Solved(K.engine_script(shape, 1), engine)
+    first = _launches(d.s)
+    d.s.device_solve()
+    return [first, _launches(d.s)]
+
+
+@pytest.mark.parametrize("shape,engine,compact", LAUNCH_CASES, ids=[launch_case_id(*c) for c in LAUNCH_CASES])
+def test_round_chain_launch_sequence(shape, engine, compact, monkeypatch):
+    """The launches per slot of the round engine and the frontier engine, for an unhinted and a hinted solve, equal the
+    record taken before their host side became a plan per solve and one chunk driver (round_chain_launches.json: the
+    counts depend on the control words only, not on the number of CUs, since every poll waits for the previous chunk's
+    words).  A change of the chunk policy, the compaction cadence or a kernel's place in the round shows here; a change
+    that means to alter them re-records the file."""
+    for k in list(VARIANTS[0]) + list(COMPACT) + ["LMMHIP_ROUND_HINT", "LMMHIP_CHUNK_MAX"]:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in (COMPACT if compact else {}).items():
+        monkeypatch.setenv(k, v)
+    with open(LAUNCH_RECORD) as f:
+        want = json.load(f)["launches"][launch_case_id(shape, engine, compact)]
+    got = launch_counts(shape, engine)
+    assert len(got[0]) == 8 and len(got[1]) == 8
+    assert got == want, (got, want)
 
 
 def _mutations(step, vkeys, ckeys):

@@ -342,7 +342,7 @@ def _hint_steps(s, ids, step):
 
 @pytest.mark.parametrize("engine", [L.System.ENGINE_ROUNDS, L.System.ENGINE_FRONTIER])
 def test_round_hint_other_round_counts_bit_identical(engine):
-    """The chunked polls end a chunk where the previous solve of the context ended (round_hint_chunk, lmm_hip_maxmin.hip):
+    """The chunked polls end a chunk where the previous solve of the context ended (round_hint_chunk, lmm_chunk.hpp; run_chunks, lmm_hip_maxmin.hip):
     a solve that takes more or fewer rounds than the previous one must still give a fresh context's bytes."""
     build = _synthetic(20000, 200000, 5, False)
     s = L.System(False)
