@@ -129,6 +129,7 @@ struct FlatBufs {
 // (LMMHIP_RDQ)
 struct RoundEngine {
   Scr crec[3], rdq[2], rqst, useg, ucnt;
+  Scr cmpbits;  // 16-B-record mode (LMMHIP_CMP_ROWS): the compaction count's alive bits, one per row
 };
 // What one round-engine solve launches (round_plan: the context, the system's sizes and the environment, read once per
 // solve — tests change the environment between solves); const from there on, handed to everything that launches.
@@ -139,6 +140,8 @@ struct RoundPlan {
   // mode: row records (short rows, LMMHIP_CREC); with them the ready queue in place of the mm_ready pass (LMMHIP_RDQ)
   // and the filter retiring the rows of saturated targets (LMMHIP_SATKEY)
   bool crec = false, rdq = false, satkey = false;
+  // with the row records: their 16-B form, which lets a compaction leave the elements in place (LMMHIP_CMP_ROWS)
+  bool rows = false;
   // the vote: the LDS-bitmap form (null: never; one 1024-thread workgroup per CU) while the alive rows (host view) are
   // at least vote_bits_rows, else the scan form (one lane per row of the work queue / mm_vote<G>)
   VoteKernel vote_bitmap = nullptr, vote_scan = nullptr;

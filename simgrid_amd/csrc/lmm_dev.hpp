@@ -108,6 +108,12 @@ template <class T> __device__ __forceinline__ void st_rlx(T* p, T v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The round engine's packed row records (one pointer; the solve's mode says which form it holds, RoundPlan::rows).
+union RowRecs {
+  uint2* r8;   // {cvar, begin}: the row's end is the next record's begin, the elements are compacted with the rows
+  uint4* r16;  // {cvar, begin, end, 0}: offsets into the original CSR (ccol[0]), the elements stay where they are
+};
+
 struct Dev {
   int32_t nV, nC;
   int64_t nnz;
@@ -197,7 +203,7 @@ struct Dev {
   int32_t* rqst;     // [nC] the round a constraint was last queued for (one entry per constraint and round)
   int32_t* useg;     // [blocks x kUSeg] the update's ready candidates for the next round, a segment per workgroup
   int32_t* ucnt;     // [blocks] their counts
-  uint2* crec[3];    // round engine, short rows: per alive row {cvar, crow} in one 8-B record (vote_row)
+  RowRecs crec[3];   // round engine, short rows: per alive row one packed record (vote_row), in the solve's form
   int32_t* ctl;     // control words
   // one-context FairBottleneck: pinned host words fbk_share writes itself (system scope) — [0] rounds started, [1] 1
   // once the solve is over — by which the host paces its rounds without a control-word copy kernel per round

@@ -99,6 +99,12 @@ constexpr VoteKernels kVoteTable[6][2] = {
     {{nullptr, mm_vote<16>}, {nullptr, mm_vote<16>}},
     {{nullptr, mm_vote<32>}, {nullptr, mm_vote<32>}},
     {{nullptr, mm_vote<64>}, {nullptr, mm_vote<64>}}};
+// The row-record forms (rows 1 and 2 above) on the 16-B records (LMMHIP_CMP_ROWS): [ready queue][sat-key filter]
+constexpr VoteKernels kVoteRowsTable[2][2] = {
+    {{mm_vote_lane<kVBlock, true, 0, true, false, false, true>, mm_vote_lane<kBlock, false, 0, true, false, false, true>},
+     {mm_vote_lane<kVBlock, true, 0, true, false, true, true>, mm_vote_lane<kBlock, false, 0, true, false, true, true>}},
+    {{mm_vote_lane<kVBlock, true, 0, true, true, false, true>, mm_vote_lane<kBlock, false, 0, true, true, false, true>},
+     {mm_vote_lane<kVBlock, true, 0, true, true, true, true>, mm_vote_lane<kBlock, false, 0, true, true, true, true>}}};
 // Saturation: [mm_ready's list, the ready queue][1, 2, 4 waves per ready constraint]
 constexpr SatKernel kSatTable[2][3] = {{mm_saturate<1>, mm_saturate<2>, mm_saturate<4>},
                                        {mm_saturate_q<1>, mm_saturate_q<2>, mm_saturate_q<4>}};
@@ -135,8 +141,12 @@ static RoundPlan round_plan(const lmmhip_ctx* c, const Dev& d) {
   // the filter retires the rows of saturated targets on the key it gathered (kSatKey, vote_waves) and the re-votes read
   // no variable state (the row-record forms of the short-row vote).  LMMHIP_SATKEY=0: the state-read path
   P.satkey = env_int("LMMHIP_SATKEY", 1) != 0;
+  // the 16-B row records {cvar, begin, end, 0}: a re-vote loads one record and reads its elements from the original
+  // CSR, and a compaction moves the per-row words only (cmp_count_rows / cmp_write_rows).  LMMHIP_CMP_ROWS=0: the 8-B
+  // records and the compaction that copies the alive rows' elements
+  P.rows = P.crec && env_int("LMMHIP_CMP_ROWS", 1) != 0;
   const int row = short_rows ? (P.rdq ? 2 : P.crec ? 1 : 0) : c->group == 16 ? 3 : c->group == 32 ? 4 : 5;
-  const VoteKernels& vk = kVoteTable[row][P.satkey];
+  const VoteKernels& vk = P.rows ? kVoteRowsTable[P.rdq][P.satkey] : kVoteTable[row][P.satkey];
   // the LDS bitmap of changed constraints (one 1024-thread workgroup per CU); below LMMHIP_VOTE_BITS_ROWS alive rows
   // (host view, A/B knob; 0 = always) the change stamps gathered per row instead: no ~125-KB copy per CU
   // (LMMHIP_VOTE_BITS=0: always the stamps' path)
@@ -189,11 +199,16 @@ static RoundPlan round_plan(const lmmhip_ctx* c, const Dev& d) {
 
 // The plan's buffers, into the solve's own Dev: the context's never carries them (lmm_dev.hpp), so no other engine —
 // whose compactions do not maintain the row records — ever sees them.
-static int round_buffers(lmmhip_ctx* c, Dev& d, const RoundPlan& P) {
+// (cmpbits: the compaction's alive bits, 16-B-record mode only — an argument of its two kernels, not part of the Dev)
+static int round_buffers(lmmhip_ctx* c, Dev& d, const RoundPlan& P, uint8_t** cmpbits) {
   if (P.crec)
     for (int k = 0; k < 3; k++)
-      if (int rc = scratch(c, c->rounds.crec[k], int64_t(d.nV) + 1, &d.crec[k]))
+      if (int rc = P.rows ? scratch(c, c->rounds.crec[k], int64_t(d.nV) + 1, &d.crec[k].r16)
+                          : scratch(c, c->rounds.crec[k], int64_t(d.nV) + 1, &d.crec[k].r8))
         return rc;
+  if (P.rows)
+    if (int rc = scratch(c, c->rounds.cmpbits, (int64_t(d.nV) + kCompactRows - 1) / kCompactRows * kBlock, cmpbits))
+      return rc;
   if (P.rdq) {
     const int64_t n = std::max<int64_t>(d.nC, 1);
     if (int rc = scratch(c, c->rounds.rdq[0], n, &d.rdq[0]) | scratch(c, c->rounds.rdq[1], n, &d.rdq[1]) |
@@ -226,10 +241,11 @@ int solve_maxmin(lmmhip_ctx* c, double prec) {
   c->ran_engine = LMMHIP_RAN_ROUNDS;
   Dev d = c->d;  // (a copy, as in the other engines: the mode's buffers go into it alone)
   const RoundPlan P = round_plan(c, d);
-  if (int rc = round_buffers(c, d, P))
+  uint8_t* cmpbits = nullptr;
+  if (int rc = round_buffers(c, d, P, &cmpbits))
     return rc;
   LAUNCH(0, -1, mm_init_cnsts, P.g_init_c, kBlock, d, prec);
-  LAUNCH(1, -1, mm_init_vars, grid_for(d.nV, kBlock), kBlock, d);
+  LAUNCH(1, -1, mm_init_vars, grid_for(d.nV, kBlock), kBlock, d, int(P.rows));
   LAUNCH(1, -1, mm_clist, std::min(P.g_c, 2 * c->n_cu), kBlock, d, 1);
   HIPCHK(hipMemsetAsync(d.chgbits, 0, sizeof(uint64_t) * ((d.nC + 127) / 128 * 2 + 2), c->stream));
   // Host view of the sizes (upper bounds: rows and constraints only leave), refreshed at every poll; they
@@ -260,9 +276,15 @@ int solve_maxmin(lmmhip_ctx* c, double prec) {
     }
     if (r - last_compact >= P.cmp_every && nrows > 4096) {  // order-preserving compaction of the alive rows
       const int nblk = int((nrows + kCompactRows - 1) / kCompactRows);
-      LAUNCH(6, r, cmp_count, nblk, kBlock, d);
-      LAUNCH(6, r, cmp_scan, 1, 1024, d, nblk, P.cmp_pct);
-      LAUNCH(6, r, cmp_write, nblk, kBlock, d);
+      if (P.rows) {
+        LAUNCH(6, r, cmp_count_rows, nblk, kBlock, d, cmpbits);
+        LAUNCH(6, r, cmp_scan<true>, 1, 1024, d, nblk, P.cmp_pct);
+        LAUNCH(6, r, cmp_write_rows, nblk, kBlock, d, cmpbits);
+      } else {
+        LAUNCH(6, r, cmp_count, nblk, kBlock, d);
+        LAUNCH(6, r, cmp_scan<false>, 1, 1024, d, nblk, P.cmp_pct);
+        LAUNCH(6, r, cmp_write, nblk, kBlock, d);
+      }
       last_compact = r;
       cm = true;
     }

@@ -95,8 +95,9 @@ __global__ void __launch_bounds__(kBlock) mm_init_cnsts(Dev s, double prec) {
   init_cnsts_waves(s, prec, wave, int64_t(gridDim.x) * (kBlock / kWave));
 }
 
-// kRec: also the packed row records of buffer 0 (the multi-launch engine's init only).
-template <bool kRec = false>
+// kRec: also the packed row records of buffer 0 (the multi-launch engine's init only); kRow: in their 16-B form
+// {cvar, begin, end, 0} (RowRecs::r16).
+template <bool kRec = false, bool kRow = false>
 __device__ __forceinline__ void init_vars_range(const Dev& s, int64_t t, int64_t nthreads) {
   for (int64_t v = t; v < s.nV; v += nthreads) {
     s.x[v] = 0.0;
@@ -104,18 +105,25 @@ __device__ __forceinline__ void init_vars_range(const Dev& s, int64_t t, int64_t
     s.rtgt[0][v] = kUnvoted;
     const int32_t cv = int32_t(v) | (s.vbound[v] > 0 ? int32_t(0x80000000u) : 0);
     const_cast<int32_t*>(s.cvar[0])[v] = cv;
-    if (kRec && s.crec[0])
-      s.crec[0][v] = make_uint2(uint32_t(cv), s.var_ptr[v]);
+    if (kRec && kRow)
+      s.crec[0].r16[v] = make_uint4(uint32_t(cv), s.var_ptr[v], s.var_ptr[v + 1], 0u);
+    else if (kRec && s.crec[0].r8)
+      s.crec[0].r8[v] = make_uint2(uint32_t(cv), s.var_ptr[v]);
   }
 }
 
-__global__ void __launch_bounds__(kBlock) mm_init_vars(Dev s) {
-  init_vars_range<true>(s, int64_t(blockIdx.x) * kBlock + threadIdx.x, int64_t(gridDim.x) * kBlock);
+// rows: the records are the 16-B ones, which need no sentinel behind the last row.
+__global__ void __launch_bounds__(kBlock) mm_init_vars(Dev s, int rows) {
+  const int64_t t = int64_t(blockIdx.x) * kBlock + threadIdx.x, nthreads = int64_t(gridDim.x) * kBlock;
+  if (rows)
+    init_vars_range<true, true>(s, t, nthreads);
+  else
+    init_vars_range<true>(s, t, nthreads);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     s.ctl[CTL_NROWS + 0] = s.nV;
     s.ctl[CTL_NELEM + 0] = int32_t(s.nnz);
-    if (s.crec[0])
-      s.crec[0][s.nV] = make_uint2(0u, s.var_ptr[s.nV]);
+    if (!rows && s.crec[0].r8)
+      s.crec[0].r8[s.nV] = make_uint2(0u, s.var_ptr[s.nV]);
   }
 }
 
@@ -448,22 +456,29 @@ constexpr int kFilt = LMM_KFILT;  // rows per lane per filter step (their loads 
 // kSat: the caller's filter retires the rows of saturated targets itself (vote_waves, kSatRet), so a row that has
 // voted before and reaches here has an alive variable: its state is not read.  Only a row that never voted
 // (kUnvoted) still reads it.
-template <int R, bool kRec = false, bool kRdq = false, bool kSat = false>
+// kRow (with kRec): the records are the 16-B ones {cvar, begin, end, 0}, one load, and the row's elements are read
+// from the original CSR whatever the buffer (the compaction moves the per-row words only, cmp_write_rows).
+template <int R, bool kRec = false, bool kRdq = false, bool kSat = false, bool kRow = false>
 __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64_t row, int* st_rows,
                                          int* st_elems, const uint16_t* __restrict__ key, int* rdq_c = nullptr,
                                          Anat an = Anat()) {
   an.restart();
   const int32_t* __restrict__ cvar = s.cvar[buf];
   const uint32_t* __restrict__ crow = s.crow[buf];
-  const int32_t* __restrict__ ccol = s.ccol[buf];
+  const int32_t* __restrict__ ccol = s.ccol[kRow ? 0 : buf];
   int32_t* __restrict__ rtgt = s.rtgt[buf];
   uint16_t* __restrict__ skey = s.skey[buf];
   // (key: s.key, or its copy in LDS — persistent engine, small systems)
   const int t = rtgt[row];
   int32_t cv;
   uint32_t b, e;
-  if (kRec) {  // (the row's variable and CSR range from one 8-B record and its successor)
-    const uint2 r0 = s.crec[buf][row], r1 = s.crec[buf][row + 1];
+  if (kRec && kRow) {
+    const uint4 r = s.crec[buf].r16[row];
+    cv = int32_t(r.x);
+    b = r.y;
+    e = r.z;
+  } else if (kRec) {  // (the row's variable and CSR range from one 8-B record and its successor)
+    const uint2 r0 = s.crec[buf].r8[row], r1 = s.crec[buf].r8[row + 1];
     cv = int32_t(r0.x);
     b = r0.y;
     e = r1.y;
@@ -648,7 +663,8 @@ __device__ __forceinline__ void vote_wave_range(int64_t lo, int64_t hi, int64_t&
 
 // an: the filter steps and re-vote batches of this wave (lv[6] filter loads, lv[7] filter gathers, lv[8] re-vote
 // batches; counters 0 steps, 1 batches); ar: vote_row's levels.
-template <bool kBits, int R, int F, int kDiag, bool kRec = false, bool kRdq = false, bool kSatRet = false>
+template <bool kBits, int R, int F, int kDiag, bool kRec = false, bool kRdq = false, bool kSatRet = false,
+          bool kRow = false>
 __device__ __forceinline__ int vote_waves(const Dev& s, int buf, int round, int64_t lo, int64_t hi,
                                           const uint64_t* bits, int* qw, int* st_rows, int* st_elems,
                                           const uint16_t* __restrict__ key, RdqLds* rql = nullptr, Anat an = Anat(),
@@ -743,7 +759,7 @@ __device__ __forceinline__ int vote_waves(const Dev& s, int buf, int round, int6
         an.restart();
         an.count(1);
         if (kDiag == 0)
-          vote_row<R, kRec, kRdq, kSatRet>(s, buf, round, row, st_rows, st_elems, key, &pc, ar);
+          vote_row<R, kRec, kRdq, kSatRet, kRow>(s, buf, round, row, st_rows, st_elems, key, &pc, ar);
         if (kRdq && kDiag == 0)
           rdq_push_lds(s, pc, round, rql);
         an.level(8, 0u);
@@ -757,7 +773,7 @@ __device__ __forceinline__ int vote_waves(const Dev& s, int buf, int round, int6
   }
   int pc = -1;
   if (kDiag == 0 && lane < qn)
-    vote_row<R, kRec, kRdq, kSatRet>(s, buf, round, qw[lane], st_rows, st_elems, key, &pc, ar);
+    vote_row<R, kRec, kRdq, kSatRet, kRow>(s, buf, round, qw[lane], st_rows, st_elems, key, &pc, ar);
   if (kRdq && kDiag == 0)
     rdq_push_lds(s, pc, round, rql);
   if (an.on() && qn > 0)
@@ -841,7 +857,8 @@ __global__ void __launch_bounds__(kBlock) mm_vote_diagcount(Dev s, int round) {
 constexpr int kVBlock = 1024;
 // (Round 5 measured the first filter step's loads issued before the bitmap copy: 24.313 / 24.390 ms against 24.340 /
 // 24.309 without, profiles/r05_ab_c2_spec2.json — neutral, the copy is not the vote's critical path; removed.)
-template <int B, bool kBits, int kDiag = 0, bool kRec = false, bool kRdq = false, bool kSatRet = false>
+template <int B, bool kBits, int kDiag = 0, bool kRec = false, bool kRdq = false, bool kSatRet = false,
+          bool kRow = false>
 __global__ void __launch_bounds__(B) mm_vote_lane(Dev s, int round) {
   AnatWave aw, awr;  // (the wave's filter steps and batches; vote_row's levels)
   const Anat an = kDiag == 0 ? aw.open(s, round, ANAT_VOTE) : Anat();
@@ -879,9 +896,9 @@ __global__ void __launch_bounds__(B) mm_vote_lane(Dev s, int round) {
   }
   int nq = 0;
   if (lo < hi)
-    nq = vote_waves<kBits, 8, kFilt, kDiag, kRec, kRdq, kSatRet>(s, buf, round, lo, hi, bits,
-                                                                 q + (threadIdx.x / kWave) * kQW, &st_rows, &st_elems,
-                                                                 s.key, &rql, an, ar);
+    nq = vote_waves<kBits, 8, kFilt, kDiag, kRec, kRdq, kSatRet, kRow>(s, buf, round, lo, hi, bits,
+                                                                       q + (threadIdx.x / kWave) * kQW, &st_rows,
+                                                                       &st_elems, s.key, &rql, an, ar);
   if (kRdq && kDiag == 0)
     rdq_flush_lds(s, round, &rql);
   if (an.on()) {  // the wave's record (vote_row's levels: the slowest lane of the wave)
@@ -1684,9 +1701,50 @@ __global__ void __launch_bounds__(kBlock) cmp_count(Dev s) {
   }
 }
 
+// The count in the 16-B-record mode (LMMHIP_CMP_ROWS): the records give the rows' variables and lengths (end - begin:
+// CTL_NELEM is kept as before).  Rows are visited k-major, as cmp_write_rows visits them (row = base + k * kBlock +
+// thread: a wave's 64 records of a step are 1 KB in a row), and the thread leaves the alive bits of its
+// kRowsPerThread rows, bit k for step k, in its own byte of `alive` ([workgroups x kBlock]), which the same thread
+// of the same workgroup of cmp_write_rows reads back.
+__global__ void __launch_bounds__(kBlock) cmp_count_rows(Dev s, uint8_t* __restrict__ alive) {
+  static_assert(kRowsPerThread == 8, "one byte of alive bits per thread");
+  if (s.ctl[CTL_DONE])
+    return;
+  const int in = s.ctl[CTL_BUF];
+  __shared__ int sh[2 * kBlock];
+  const int64_t nrows = s.ctl[CTL_NROWS + in];
+  const int64_t base = int64_t(blockIdx.x) * kCompactRows + threadIdx.x;
+  const uint4* __restrict__ rec = s.crec[in].r16;
+  uint4 rr[kRowsPerThread];
+#pragma unroll
+  for (int k = 0; k < kRowsPerThread; k++)
+    rr[k] = base + k * kBlock < nrows ? rec[base + k * kBlock] : make_uint4(0u, 0u, 0u, 0u);
+  bool al[kRowsPerThread];
+#pragma unroll
+  for (int k = 0; k < kRowsPerThread; k++)
+    al[k] = base + k * kBlock < nrows && s.vstate[rvar(int32_t(rr[k].x))] == 0;
+  int nr = 0, ne = 0;
+  unsigned bits = 0;
+#pragma unroll
+  for (int k = 0; k < kRowsPerThread; k++)
+    if (al[k]) {
+      nr++;
+      ne += int(rr[k].z - rr[k].y);
+      bits |= 1u << k;
+    }
+  alive[int64_t(blockIdx.x) * kBlock + threadIdx.x] = uint8_t(bits);
+  int a = nr, b = ne;
+  block_scan2(a, b, sh);
+  if (threadIdx.x == kBlock - 1) {
+    s.bsum[2 * blockIdx.x] = a + nr;
+    s.bsum[2 * blockIdx.x + 1] = b + ne;
+  }
+}
+
 // Exclusive scan of the per-block counts, totals into the output buffer's words, and the decision: rewrite
 // only when fewer than pct % of the scanned rows are alive (CTL_CMPGO).
-__global__ void __launch_bounds__(1024) cmp_scan(Dev s, int nblk, int pct) {
+// kRows: the 16-B-record mode, which has no row-offset array and no sentinel record to close.
+template <bool kRows = false> __global__ void __launch_bounds__(1024) cmp_scan(Dev s, int nblk, int pct) {
   if (s.ctl[CTL_DONE])
     return;
   const int in = s.ctl[CTL_BUF], out = in == 1 ? 2 : 1;
@@ -1722,9 +1780,11 @@ __global__ void __launch_bounds__(1024) cmp_scan(Dev s, int nblk, int pct) {
     if (go) {
       s.ctl[CTL_NROWS + out] = sa[t];
       s.ctl[CTL_NELEM + out] = sb[t];
-      const_cast<uint32_t*>(s.crow[out])[sa[t]] = uint32_t(sb[t]);
-      if (s.crec[out])
-        s.crec[out][sa[t]] = make_uint2(0u, uint32_t(sb[t]));
+      if (!kRows) {
+        const_cast<uint32_t*>(s.crow[out])[sa[t]] = uint32_t(sb[t]);
+        if (s.crec[out].r8)
+          s.crec[out].r8[sa[t]] = make_uint2(0u, uint32_t(sb[t]));
+      }
     }
   }
 }
@@ -1794,8 +1854,8 @@ __global__ void __launch_bounds__(kBlock) cmp_write(Dev s) {
     if (al) {
       const int o = pr + xr;
       ovar[o] = v;
-      if (s.crec[out])
-        s.crec[out][o] = make_uint2(uint32_t(v), uint32_t(pe + xe));
+      if (s.crec[out].r8)
+        s.crec[out].r8[o] = make_uint2(uint32_t(v), uint32_t(pe + xe));
       s.rtgt[out][o] = s.rtgt[in][row];
       s.skey[out][o] = s.skey[in][row];
       orow[o] = uint32_t(pe + xe);
@@ -1820,6 +1880,71 @@ __global__ void __launch_bounds__(kBlock) cmp_write(Dev s) {
     pr += tr;
     pe += te;
   }
+}
+
+// The write in the 16-B-record mode: only the per-row words move (record, cvar, rtgt, skey).  The records carry
+// their rows' ranges in the original CSR, and the elements never change during a solve, so there is no element copy,
+// no search for an element's row, and neither crow[out] nor ccol[out] is written.
+// The rows' alive bits come from cmp_count_rows' bitmap instead of a second cvar -> vstate gather: nothing between the
+// two launches changes a variable's state (cmp_scan alone runs between them, and the stream is in order).
+// Rows are visited k-major as in cmp_write; the block's kRowsPerThread steps are scanned together (one barrier) and
+// their loads are in flight together.
+__global__ void __launch_bounds__(kBlock) cmp_write_rows(Dev s, const uint8_t* __restrict__ alive) {
+  if (s.ctl[CTL_DONE] || !s.ctl[CTL_CMPGO])
+    return;
+  const int in = s.ctl[CTL_BUF], out = in == 1 ? 2 : 1;
+  const int64_t base = int64_t(blockIdx.x) * kCompactRows;
+  const int pr = s.bsum[2 * blockIdx.x];
+  __shared__ int wcnt[kRowsPerThread][kBlock / kWave];
+  const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+  const unsigned long long below = (1ull << lane) - 1;
+  bool al[kRowsPerThread];
+  int pos[kRowsPerThread];
+  // (this thread's byte of cmp_count_rows, launched over the same workgroups: bit k = its row of step k)
+  const unsigned bits = alive[int64_t(blockIdx.x) * kBlock + threadIdx.x];
+#pragma unroll
+  for (int k = 0; k < kRowsPerThread; k++) {
+    al[k] = (bits >> k) & 1;
+    const unsigned long long m = __ballot(al[k]);
+    pos[k] = __popcll(m & below);
+    if (lane == 0)
+      wcnt[k][w] = __popcll(m);
+  }
+  __syncthreads();
+  int run = pr;  // output row of the step's first alive row
+#pragma unroll
+  for (int k = 0; k < kRowsPerThread; k++) {
+    int off = run;
+#pragma unroll
+    for (int i = 0; i < kBlock / kWave; i++) {
+      off += i < w ? wcnt[k][i] : 0;
+      run += wcnt[k][i];
+    }
+    pos[k] += off;
+  }
+  const uint4* __restrict__ irec = s.crec[in].r16;
+  const int32_t* __restrict__ itgt = s.rtgt[in];
+  const uint16_t* __restrict__ ikey = s.skey[in];
+  uint4 rr[kRowsPerThread];
+  int32_t tg[kRowsPerThread];
+  unsigned sk[kRowsPerThread];
+#pragma unroll
+  for (int k = 0; k < kRowsPerThread; k++) {
+    const int64_t row = base + int64_t(k) * kBlock + threadIdx.x;
+    rr[k] = al[k] ? irec[row] : make_uint4(0u, 0u, 0u, 0u);
+    tg[k] = al[k] ? itgt[row] : 0;
+    sk[k] = al[k] ? unsigned(ikey[row]) : 0u;
+  }
+  int32_t* ovar = const_cast<int32_t*>(s.cvar[out]);
+#pragma unroll
+  for (int k = 0; k < kRowsPerThread; k++)
+    if (al[k]) {
+      const int o = pos[k];
+      s.crec[out].r16[o] = rr[k];
+      ovar[o] = int32_t(rr[k].x);
+      s.rtgt[out][o] = tg[k];
+      s.skey[out][o] = uint16_t(sk[k]);
+    }
 }
 
 }  // namespace lmmdev
