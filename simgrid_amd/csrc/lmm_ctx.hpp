@@ -148,7 +148,8 @@ struct RoundPlan {
   int64_t vote_bits_rows = 0;
   SatKernel saturate = nullptr;  // mm_saturate<K> / mm_saturate_q<K>
   int sat_waves = 4;             // its K: waves per ready constraint
-  UpdKernel update = nullptr;    // mm_update<rdq>
+  bool upd_quad = false;         // the update's touched records as one 64-B request per quad (LMMHIP_UPD_QUAD)
+  UpdKernel update = nullptr;    // mm_update<rdq, upd_quad>
   // grids and caps
   int g_init_c = 1, g_c = 1;  // mm_init_cnsts (a wave per constraint), thread per constraint
   int g_upd = 1;              // mm_update and mm_done's argument: capped identity grid, or the ready-queue segments'

@@ -108,7 +108,9 @@ constexpr VoteKernels kVoteRowsTable[2][2] = {
 // Saturation: [mm_ready's list, the ready queue][1, 2, 4 waves per ready constraint]
 constexpr SatKernel kSatTable[2][3] = {{mm_saturate<1>, mm_saturate<2>, mm_saturate<4>},
                                        {mm_saturate_q<1>, mm_saturate_q<2>, mm_saturate_q<4>}};
-constexpr UpdKernel kUpdTable[2] = {mm_update<false>, mm_update<true>};
+// Update: [mm_ready's list, the ready queue][records lane by lane, one 64-B request per quad]
+constexpr UpdKernel kUpdTable[2][2] = {{mm_update<false, false>, mm_update<false, true>},
+                                       {mm_update<true, false>, mm_update<true, true>}};
 
 static RoundPlan round_plan(const lmmhip_ctx* c, const Dev& d) {
   RoundPlan P;
@@ -159,7 +161,10 @@ static RoundPlan round_plan(const lmmhip_ctx* c, const Dev& d) {
   P.sat_waves = sat_k == 1 || sat_k == 2 ? sat_k : 4;
   P.saturate = kSatTable[P.rdq][P.sat_waves == 4 ? 2 : P.sat_waves - 1];
   P.sat_max = env_int("LMMHIP_SAT_GRID_MAX", kMaxBlocks);
-  P.update = kUpdTable[P.rdq];
+  // mm_update moves a touched constraint's record as one 64-B request per quad of lanes, both ways, instead of eight
+  // lane-by-lane pieces (update_groups, kQuad).  LMMHIP_UPD_QUAD=0: lane by lane
+  P.upd_quad = env_int("LMMHIP_UPD_QUAD", 1) != 0;
+  P.update = kUpdTable[P.rdq][P.upd_quad];
   P.g_init_c = grid_for(d.nC, kBlock / kWave);
   P.g_c = grid_for(d.nC, kBlock);
   // mm_update: thread per constraint, identity order (ready-queue mode: at most kUSeg constraints per workgroup)

@@ -21,6 +21,8 @@
 //                saturated constraints (maxmin.cpp:608-623), refresh ratio, key and change stamp;
 //                FATPIPE usage is recomputed over the still-unfixed elements (maxmin.cpp:625-658).
 #pragma once
+#include <type_traits>
+
 #include "lmm_dev.hpp"
 
 namespace lmmdev {
@@ -1431,11 +1433,53 @@ template <int K> __global__ void __launch_bounds__(kBlock) mm_saturate_q(Dev s, 
 // used, so a wave keeps K times the memory requests in flight.
 // (an: the steps' levels: lv[0] keys and touch flags, lv[1] touched records, lv[2] the rest; counters 0 steps,
 // 1 touched constraints)
-template <int K, bool kRdq = false>
-__device__ __forceinline__ int update_groups(const Dev& s, int64_t base0, int64_t stride, int round, double prec,
+//
+// kQuad (mm_update, LMMHIP_UPD_QUAD): a touched record moves as ONE 64-B request, both ways.  Lane by lane (kQuad
+// false) a wave loads its records with four instructions and writes them back with four more, each carrying up to 64
+// different lines.  Here the touched lanes of a group are ranked (ballot), quad `lane >> 2` of pass p serves the
+// (16 p + (lane >> 2))-th of them, and each of its four lanes moves the 16 B at record + 16 * (lane & 3): a wave
+// instruction carries at most 16 lines, a group of <= 16 touched constraints is one load and one store instruction
+// (passes past the count run with EXEC = 0).  The 64 bytes reach the owner lane — the lane whose constraint it is in
+// identity order — and come back from it through a per-wave LDS tile (UpdQuadLds), reused group by group; arithmetic,
+// FATPIPE recompute, candidate listing and ballots stay in the owner lane, so no decision or value changes.  The
+// write-back is the full line {0, 0 | 0, pad | rem, use | ratio, bound}, `pad` and `bound` as loaded.
+using u32x4 = uint32_t __attribute__((ext_vector_type(4)));  // (16 B in four registers: one b128 load / store)
+union UpdPiece {  // 16 B of a record: as one b128 access, or its two 8-B fields
+  u32x4 v;
+  unsigned long long q[2];
+};
+template <int K> struct UpdQuadLds {
+  static_assert(kWave == 64, "16 quads x 4 passes cover a group; owner lanes are 6-bit (& 63)");
+  // tile[j][l]: bytes 16 j .. 16 j + 15 of owner lane l's record (piece-major: the owner's four reads and writes are
+  // lane-contiguous)
+  UpdPiece tile[4][kWave];
+  // own[k][q]: the owner lanes quad q serves in passes 0-3, one byte each (byte p: the lane of group k's
+  // (16 p + q)-th touched constraint); written a byte at a time (set_owner), read a word at a time
+  uint32_t own[K][kWave / 4];
+  static_assert(sizeof(own[0]) == kWave, "one byte per rank of a group");
+  __device__ __forceinline__ void set_owner(int k, int r, int lane) {
+    reinterpret_cast<unsigned char*>(own[k])[4 * (r & 15) + (r >> 4)] = (unsigned char)lane;
+  }
+};
+// The lanes of ONE wave hand data to each other through LDS (UpdQuadLds): what the lanes stored before is visible to
+// the loads behind.  The wave barrier alone only pins the instruction schedule; the wavefront-scope fences make the
+// ordering part of the memory model instead of a consequence of what the optimizer can prove about aliasing (in
+// hardware a wave's DS instructions execute in order: the fences cost no instruction).
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+template <int K, bool kRdq = false, bool kQuad = false>
+__device__ __forceinline__ int update_groups(const Dev& s, int64_t wbase, int64_t stride, int round, double prec,
                                              bool* touch, int* ucnt_sh = nullptr, int32_t* ulist = nullptr,
-                                             Anat an = Anat()) {
+                                             Anat an = Anat(), UpdQuadLds<K>* ql = nullptr) {
   const int lane = threadIdx.x & (kWave - 1);
+  // (kQuad: the wave's base as the scalar it is — the groups' addresses are then a scalar base and a 32-bit lane
+  // offset instead of 64-bit registers per array and group, which the quad pieces' registers leave no room for)
+  const int64_t base0 = kQuad ? int64_t(uint32_t(__builtin_amdgcn_readfirstlane(int(wbase)))) |
+                                    int64_t(__builtin_amdgcn_readfirstlane(int(wbase >> 32))) << 32
+                              : wbase;
   an.restart();
   an.count(0);
   unsigned okey[K], tf[K];
@@ -1455,29 +1499,73 @@ __device__ __forceinline__ int update_groups(const Dev& s, int64_t base0, int64_
   unsigned long long qx[K], qy[K], qz[K];
   double rem[K], use[K], bnd[K];
   int32_t ce[K], nv[K];
+  // (kQuad) per group: the touched and the saturated lanes, the owner lanes this lane's quad serves in passes 0-3 (a
+  // byte each), the passes' 16-B pieces
+  unsigned long long tm[kQuad ? K : 1], sm[kQuad ? K : 1];
+  uint32_t ow[kQuad ? K : 1];
+  u32x4 pc[kQuad ? K : 1][4];
+  const int qr = lane >> 2, qp = lane & 3;  // the quad's rank within a pass, the lane's 16-B piece of the record
+  if constexpr (!kQuad) {
 #pragma unroll
-  for (int k = 0; k < K; k++) {
-    const int64_t c = base0 + k * stride + lane;
-    qx[k] = qy[k] = qz[k] = 0;
-    rem[k] = use[k] = bnd[k] = 0.0;
-    ce[k] = nv[k] = 0;
-    if (!key_dead(okey[k]) && tf[k] == 1) {  // an untouched constraint keeps its record as it is
-      const CstRec* rec = s.cst + c;
-      qx[k] = rec->drem;
-      qy[k] = rec->duse;
-      qz[k] = rec->dcnt;
-      rem[k] = rec->rem;
-      use[k] = rec->use;
-      bnd[k] = rec->bound;
-      ce[k] = s.cexp[c];
-      nv[k] = s.nvote[c];
+    for (int k = 0; k < K; k++) {
+      const int64_t c = base0 + k * stride + lane;
+      qx[k] = qy[k] = qz[k] = 0;
+      rem[k] = use[k] = bnd[k] = 0.0;
+      ce[k] = nv[k] = 0;
+      if (!key_dead(okey[k]) && tf[k] == 1) {  // an untouched constraint keeps its record as it is
+        const CstRec* rec = s.cst + c;
+        qx[k] = rec->drem;
+        qy[k] = rec->duse;
+        qz[k] = rec->dcnt;
+        rem[k] = rec->rem;
+        use[k] = rec->use;
+        bnd[k] = rec->bound;
+        ce[k] = s.cexp[c];
+        nv[k] = s.nvote[c];
+      }
+    }
+  } else {
+    const unsigned long long below = (1ull << lane) - 1;
+#pragma unroll
+    for (int k = 0; k < K; k++) {  // rank the touched lanes of every group: own[k][rank] = lane
+      const bool t = !key_dead(okey[k]) && tf[k] == 1;
+      tm[k] = __ballot(t);
+      sm[k] = __ballot(!key_dead(okey[k]) && tf[k] == 2);  // (the flags as wave masks from here on: registers)
+      if (t)
+        ql->set_owner(k, __popcll(tm[k] & below), lane);
+    }
+    wave_lds_sync();
+#pragma unroll
+    for (int k = 0; k < K; k++)  // (bytes of ranks past the count are stale: never used)
+      ow[k] = ql->own[k][qr];
+#pragma unroll
+    for (int k = 0; k < K; k++) {  // every group's loads, before any is used
+      const int64_t gbase = base0 + k * stride;
+      const int n = __popcll(tm[k]);
+      ce[k] = nv[k] = 0;
+      if ((tm[k] >> lane) & 1) {  // (the owner's own words: as lane by lane)
+        ce[k] = s.cexp[gbase + lane];
+        nv[k] = s.nvote[gbase + lane];
+      }
+#pragma unroll
+      for (int p = 0; p < 4; p++)
+        if (16 * p + qr < n)  // (owner lanes are touched lanes: below nC)
+          pc[k][p] = reinterpret_cast<const u32x4*>(s.cst + (gbase + ((ow[k] >> (8 * p)) & 63)))[qp];
     }
   }
   if (an.on()) {
     double rs = 0.0;
 #pragma unroll
     for (int k = 0; k < K; k++) {
-      rs += rem[k] + use[k] + bnd[k] + double(qx[k] + qy[k] + qz[k]) + double(ce[k] + nv[k]);
+      if constexpr (!kQuad) {
+        rs += rem[k] + use[k] + bnd[k] + double(qx[k] + qy[k] + qz[k]) + double(ce[k] + nv[k]);
+      } else {
+        rs += double(ce[k] + nv[k]);
+#pragma unroll
+        for (int p = 0; p < 4; p++)
+          if (16 * p + qr < __popcll(tm[k]))
+            rs += double(pc[k][p].x + pc[k][p].y + pc[k][p].z + pc[k][p].w);
+      }
       an.count(1, unsigned(__popcll(__ballot(!key_dead(okey[k]) && tf[k] == 1))));
     }
     an.level(1, rs);
@@ -1490,9 +1578,29 @@ __device__ __forceinline__ int update_groups(const Dev& s, int64_t base0, int64_
       break;
     const int64_t c = gbase + lane;
     const bool live0 = !key_dead(okey[k]);
-    const bool sat = live0 && tf[k] == 2;
+    const bool sat = kQuad ? bool((sm[kQuad ? k : 0] >> lane) & 1) : live0 && tf[k] == 2;
     const bool live = live0 && !sat;
-    const bool tch = live && tf[k] == 1;
+    const bool tch = kQuad ? bool((tm[kQuad ? k : 0] >> lane) & 1) : live && tf[k] == 1;
+    if constexpr (kQuad) {  // the quads' pieces to their owner lanes
+      const int n = __popcll(tm[k]);
+      const uint32_t o4 = ql->own[k][qr];  // (read again: ow[k] ends at the loads)
+#pragma unroll
+      for (int p = 0; p < 4; p++)
+        if (16 * p + qr < n)
+          ql->tile[qp][(o4 >> (8 * p)) & 63].v = pc[k][p];
+      wave_lds_sync();
+      qx[k] = qy[k] = qz[k] = 0;
+      rem[k] = use[k] = bnd[k] = 0.0;
+      if (tch) {  // (`pad` and `ratio` are not read: they stay in the tile)
+        const u32x4 a = ql->tile[0][lane].v, b = ql->tile[1][lane].v, d = ql->tile[2][lane].v, e = ql->tile[3][lane].v;
+        qx[k] = a.x | (unsigned long long)a.y << 32;
+        qy[k] = a.z | (unsigned long long)a.w << 32;
+        qz[k] = b.x | (unsigned long long)b.y << 32;
+        rem[k] = __longlong_as_double((long long)(d.x | (unsigned long long)d.y << 32));
+        use[k] = __longlong_as_double((long long)(d.z | (unsigned long long)d.w << 32));
+        bnd[k] = __longlong_as_double((long long)(e.z | (unsigned long long)e.w << 32));
+      }
+    }
     const bool fat = tch && (ce[k] & kCexpFat);
     // FATPIPE: recompute only when a removed element reached the usage (fat_bits in duse)
     const bool fre = fat && !(__longlong_as_double((long long)qy[k]) < use[k]);
@@ -1515,6 +1623,7 @@ __device__ __forceinline__ int update_groups(const Dev& s, int64_t base0, int64_
     }
     bool changed = false;
     CstRec* rec = s.cst + c;
+    double wr = 0.0, wu = 0.0, wq = 0.0;  // (kQuad) the touched record's new rem, use, ratio
     if (sat) {
       *touch = true;  // (a saturation this round: the round's CTL_LASTR, set here instead of by every ready task)
       s.key[c] = kSatKey;  // (its voters were all fixed with it: the next filter retires their rows on this key)
@@ -1529,7 +1638,8 @@ __device__ __forceinline__ int update_groups(const Dev& s, int64_t base0, int64_
       } else {
         *touch = true;
         s.ctouch[c] = 0;
-        rec->drem = rec->duse = rec->dcnt = 0;
+        if constexpr (!kQuad)
+          rec->drem = rec->duse = rec->dcnt = 0;
         const int nvn = nv[k] - int(qz[k]);
         s.nvote[c] = nvn;
         s.chg[c] = uint16_t(round);
@@ -1544,16 +1654,27 @@ __device__ __forceinline__ int update_groups(const Dev& s, int64_t base0, int64_
         } else {
           u0 = fuse;
         }
-        rec->rem = r0;
-        rec->use = u0;
+        if constexpr (!kQuad) {
+          rec->rem = r0;
+          rec->use = u0;
+        } else {
+          wr = r0;
+          wu = u0;
+        }
         if (!(u0 > prec) || !(r0 > bnd[k] * prec)) {
-          rec->ratio = dinf();
+          if constexpr (!kQuad)
+            rec->ratio = dinf();
+          else
+            wq = dinf();
           s.key[c] = kDeadKey;
           s.cexp[c] = kCexpDead;
           changed = true;
         } else {
           const double r = r0 / u0;
-          rec->ratio = r;
+          if constexpr (!kQuad)
+            rec->ratio = r;
+          else
+            wq = r;
           const unsigned nk = ratio_key(r);
           s.key[c] = uint16_t(nk);
           changed = nk != okey[k];
@@ -1565,6 +1686,29 @@ __device__ __forceinline__ int update_groups(const Dev& s, int64_t base0, int64_
           }
         }
       }
+    }
+    if constexpr (kQuad) {  // the touched records back through the tile: one full-line request per quad
+      if (tch) {  // (the owner's slots still hold the record as loaded: `pad` and `bound` stay as they are)
+        const unsigned long long br = (unsigned long long)__double_as_longlong(wr);
+        const unsigned long long bu = (unsigned long long)__double_as_longlong(wu);
+        const unsigned long long bq = (unsigned long long)__double_as_longlong(wq);
+        ql->tile[0][lane].v = u32x4{0u, 0u, 0u, 0u};
+        ql->tile[1][lane].q[0] = 0ull;
+        ql->tile[2][lane].v = u32x4{uint32_t(br), uint32_t(br >> 32), uint32_t(bu), uint32_t(bu >> 32)};
+        ql->tile[3][lane].q[0] = bq;
+      }
+      wave_lds_sync();
+      const int n = __popcll(tm[k]);
+      // (the owner lanes read again, not taken from ow[k]: the sixteen load addresses would otherwise stay in registers
+      // up to here, over the budget of four waves per SIMD)
+      const uint32_t o4 = ql->own[k][qr];
+#pragma unroll
+      for (int p = 0; p < 4; p++)
+        if (16 * p + qr < n) {
+          const int o = (o4 >> (8 * p)) & 63;
+          reinterpret_cast<u32x4*>(s.cst + (gbase + o))[qp] = ql->tile[qp][o].v;
+        }
+      wave_lds_sync();  // (the next group's pieces overwrite the tile)
     }
     const unsigned long long word = __ballot(changed);
     if (lane == 0)
@@ -1583,7 +1727,9 @@ __device__ __forceinline__ int update_groups(const Dev& s, int64_t base0, int64_
 #ifndef LMM_UPD_K
 #define LMM_UPD_K 4
 #endif
-template <bool kRdq = false> __global__ void __launch_bounds__(kBlock) mm_update(Dev s, int round, double prec) {
+// kQuad: the touched records move as one 64-B request per quad (update_groups; LMMHIP_UPD_QUAD, the default).
+template <bool kRdq = false, bool kQuad = false>
+__global__ void __launch_bounds__(kBlock, kQuad ? 4 : 1) mm_update(Dev s, int round, double prec) {
   AnatWave aw;
   const Anat an = aw.open(s, round, ANAT_UPD);
   const unsigned long long t_in = an.now();
@@ -1593,6 +1739,11 @@ template <bool kRdq = false> __global__ void __launch_bounds__(kBlock) mm_update
     s.ctl[CTL_ROUNDS] += 1;
   __shared__ int alive_cnt, ucnt_sh;
   __shared__ int32_t ulist[kRdq ? kUSeg : 1];
+  // (kQuad) a tile per wave: 4,352 B each, 17 KB per workgroup — four workgroups per CU keep their place
+  __shared__ std::conditional_t<kQuad, UpdQuadLds<LMM_UPD_K>, int> qlds[kBlock / kWave];
+  UpdQuadLds<LMM_UPD_K>* ql = nullptr;
+  if constexpr (kQuad)
+    ql = &qlds[threadIdx.x / kWave];
   if (threadIdx.x == 0)
     alive_cnt = ucnt_sh = 0;
   __syncthreads();
@@ -1601,7 +1752,7 @@ template <bool kRdq = false> __global__ void __launch_bounds__(kBlock) mm_update
   const int64_t stride = int64_t(gridDim.x) * kBlock;
   for (int64_t base = (int64_t(blockIdx.x) * kBlock + threadIdx.x) & ~int64_t(kWave - 1); base < s.nC;
        base += LMM_UPD_K * stride)  // wave-uniform; LMM_UPD_K groups of 64 constraints per step, loads in flight together
-    alive += update_groups<LMM_UPD_K, kRdq>(s, base, stride, round, prec, &any_touch, &ucnt_sh, ulist, an);
+    alive += update_groups<LMM_UPD_K, kRdq, kQuad>(s, base, stride, round, prec, &any_touch, &ucnt_sh, ulist, an, ql);
   const unsigned long long t_loop = an.now();
   if (alive)
     atomicAdd(&alive_cnt, alive);
