@@ -23,6 +23,7 @@
 #include "../../include/lmm/lmm_hip.h"
 #include "lmm_dev.hpp"
 #include "lmm_chunk.hpp"
+#include "lmm_round_mode.hpp"
 
 using namespace lmmdev;
 
@@ -125,11 +126,11 @@ struct FlatBufs {
 };
 
 // ---- the engines' entry points (lmmhip_solve dispatches to them) and their private state ----
-// round engine (lmm_hip_maxmin.hip solve_maxmin): packed row records (LMMHIP_CREC), ready queue / update segments
-// (LMMHIP_RDQ)
+// round engine (lmm_hip_maxmin.hip solve_maxmin), the buffers of its mode (lmm_round_mode.hpp): the packed row records
+// of RowForm Rec8 / Rec16, the vote mode's ready queue and the update's segments
 struct RoundEngine {
   Scr crec[3], rdq[2], rqst, useg, ucnt;
-  Scr cmpbits;  // 16-B-record mode (LMMHIP_CMP_ROWS): the compaction count's alive bits, one per row
+  Scr cmpbits;  // RowForm::Rec16: the compaction count's alive bits, one per row
 };
 // What one round-engine solve launches (round_plan: the context, the system's sizes and the environment, read once per
 // solve — tests change the environment between solves); const from there on, handed to everything that launches.
@@ -137,11 +138,10 @@ using VoteKernel = void (*)(Dev, int);          // (s, round)
 using SatKernel = void (*)(Dev, int, int);      // (s, round, segments)
 using UpdKernel = void (*)(Dev, int, double);   // (s, round, prec)
 struct RoundPlan {
-  // mode: row records (short rows, LMMHIP_CREC); with them the ready queue in place of the mm_ready pass (LMMHIP_RDQ)
-  // and the filter retiring the rows of saturated targets (LMMHIP_SATKEY)
-  bool crec = false, rdq = false, satkey = false;
-  // with the row records: their 16-B form, which lets a compaction leave the elements in place (LMMHIP_CMP_ROWS)
-  bool rows = false;
+  // the vote mode (lmm_round_mode.hpp): the RowForm the re-votes read (short rows: LMMHIP_CREC, LMMHIP_CMP_ROWS); on
+  // the record forms the ready queue in place of the mm_ready pass (LMMHIP_RDQ) and the filter retiring the rows of
+  // saturated targets (LMMHIP_SATKEY)
+  VoteMode mode;
   // the vote: the LDS-bitmap form (null: never; one 1024-thread workgroup per CU) while the alive rows (host view) are
   // at least vote_bits_rows, else the scan form (one lane per row of the work queue / mm_vote<G>)
   VoteKernel vote_bitmap = nullptr, vote_scan = nullptr;
@@ -149,7 +149,7 @@ struct RoundPlan {
   SatKernel saturate = nullptr;  // mm_saturate<K> / mm_saturate_q<K>
   int sat_waves = 4;             // its K: waves per ready constraint
   bool upd_quad = false;         // the update's touched records as one 64-B request per quad (LMMHIP_UPD_QUAD)
-  UpdKernel update = nullptr;    // mm_update<rdq, upd_quad>
+  UpdKernel update = nullptr;    // mm_update<UpdMode{mode.queue, upd_quad}>
   // grids and caps
   int g_init_c = 1, g_c = 1;  // mm_init_cnsts (a wave per constraint), thread per constraint
   int g_upd = 1;              // mm_update and mm_done's argument: capped identity grid, or the ready-queue segments'

@@ -29,7 +29,7 @@ enum : int {
   CTL_ANY0 = 2,      // fair bottleneck: "some variable still listed", per round parity (2 words)
   CTL_NROWS = 4,     // alive-row buffer sizes (3 buffers)
   CTL_NELEM = 7,     // alive-row buffer element counts (3 buffers)
-  CTL_ALIVE_C = 10,  // (unused since round 6)
+  // (word 10: unused)
   CTL_NREADY = 11,   // maxmin: ready-list length of the current round
   CTL_RDQ0 = 12,     // multi-launch maxmin: the vote's ready-queue lengths, per round parity (2 words; rdq)
   CTL_NCL0 = 14,     // maxmin: alive-constraint list lengths (2 buffers)
@@ -108,7 +108,8 @@ template <class T> __device__ __forceinline__ void st_rlx(T* p, T v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// The round engine's packed row records (one pointer; the solve's mode says which form it holds, RoundPlan::rows).
+// The round engine's packed row records (one pointer; the RowForm of the solve's mode, lmm_round_mode.hpp, says which
+// form it holds: Rec8 -> r8, Rec16 -> r16, Arrays -> null).
 union RowRecs {
   uint2* r8;   // {cvar, begin}: the row's end is the next record's begin, the elements are compacted with the rows
   uint4* r16;  // {cvar, begin, end, 0}: offsets into the original CSR (ccol[0]), the elements stay where they are

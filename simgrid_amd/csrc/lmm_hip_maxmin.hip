@@ -7,9 +7,11 @@
 // (policy arithmetic: lmm_chunk.hpp).  Each engine works on its own copy of the context's Dev.
 #include <cstring>
 
+#include <array>
 #include <map>
 #include <mutex>
 #include <thread>
+#include <utility>
 
 #include "lmm_ctx.hpp"
 #include "lmm_maxmin_kernels.hpp"
@@ -84,71 +86,70 @@ static int run_chunks(lmmhip_ctx* c, const Dev& d, const ChunkPolicy& p, Rounds&
   return poll_ctl(c);
 }
 
-// The round engine's kernels by mode.  Vote: rows 0-2 the short-row lane vote (no row records / row records / row
-// records + ready queue; groups of 4 and 8: one lane per row, more gathers in flight per wave), each [without, with] the
-// sat-key filter, in its LDS-bitmap form and its scan form; rows 3-5 the long-row votes mm_vote<16|32|64> (scan only).
+// The round engine's kernels by mode (lmm_round_mode.hpp).  The short-row lane vote (groups of 4 and 8: one lane per
+// row, more gathers in flight per wave): entry i is the vote mode of index i, in its LDS-bitmap form and its scan form —
+// built by enumerating the indices, so a mode cannot reach a kernel built for another.  The long-row votes
+// mm_vote<16|32|64> have the Arrays mode and the scan form only.
 struct VoteKernels {
   VoteKernel bitmap, scan;
 };
-constexpr VoteKernels kVoteTable[6][2] = {
-    {{mm_vote_lane<kVBlock, true>, mm_vote_lane<kBlock, false>}, {mm_vote_lane<kVBlock, true>, mm_vote_lane<kBlock, false>}},
-    {{mm_vote_lane<kVBlock, true, 0, true>, mm_vote_lane<kBlock, false, 0, true>},
-     {mm_vote_lane<kVBlock, true, 0, true, false, true>, mm_vote_lane<kBlock, false, 0, true, false, true>}},
-    {{mm_vote_lane<kVBlock, true, 0, true, true>, mm_vote_lane<kBlock, false, 0, true, true>},
-     {mm_vote_lane<kVBlock, true, 0, true, true, true>, mm_vote_lane<kBlock, false, 0, true, true, true>}},
-    {{nullptr, mm_vote<16>}, {nullptr, mm_vote<16>}},
-    {{nullptr, mm_vote<32>}, {nullptr, mm_vote<32>}},
-    {{nullptr, mm_vote<64>}, {nullptr, mm_vote<64>}}};
-// The row-record forms (rows 1 and 2 above) on the 16-B records (LMMHIP_CMP_ROWS): [ready queue][sat-key filter]
-constexpr VoteKernels kVoteRowsTable[2][2] = {
-    {{mm_vote_lane<kVBlock, true, 0, true, false, false, true>, mm_vote_lane<kBlock, false, 0, true, false, false, true>},
-     {mm_vote_lane<kVBlock, true, 0, true, false, true, true>, mm_vote_lane<kBlock, false, 0, true, false, true, true>}},
-    {{mm_vote_lane<kVBlock, true, 0, true, true, false, true>, mm_vote_lane<kBlock, false, 0, true, true, false, true>},
-     {mm_vote_lane<kVBlock, true, 0, true, true, true, true>, mm_vote_lane<kBlock, false, 0, true, true, true, true>}}};
+template <int... I> constexpr std::array<VoteKernels, sizeof...(I)> lane_votes(std::integer_sequence<int, I...>) {
+  return {{{mm_vote_lane<VoteForm::Bitmap, I>, mm_vote_lane<VoteForm::Scan, I>}...}};
+}
+constexpr auto kVoteTable = lane_votes(std::make_integer_sequence<int, kVoteModes>{});
+constexpr VoteKernel kVoteLong[3] = {mm_vote<16>, mm_vote<32>, mm_vote<64>};
 // Saturation: [mm_ready's list, the ready queue][1, 2, 4 waves per ready constraint]
 constexpr SatKernel kSatTable[2][3] = {{mm_saturate<1>, mm_saturate<2>, mm_saturate<4>},
                                        {mm_saturate_q<1>, mm_saturate_q<2>, mm_saturate_q<4>}};
-// Update: [mm_ready's list, the ready queue][records lane by lane, one 64-B request per quad]
-constexpr UpdKernel kUpdTable[2][2] = {{mm_update<false, false>, mm_update<false, true>},
-                                       {mm_update<true, false>, mm_update<true, true>}};
+// Update: entry i is the update mode of index i (queue, quad)
+template <int... I> constexpr std::array<UpdKernel, sizeof...(I)> updates(std::integer_sequence<int, I...>) {
+  return {{mm_update<I>...}};
+}
+constexpr auto kUpdTable = updates(std::make_integer_sequence<int, kUpdModes>{});
 
 static RoundPlan round_plan(const lmmhip_ctx* c, const Dev& d) {
   RoundPlan P;
-  const bool short_rows = c->group == 4 || c->group == 8;
-  // packed row records for the re-votes (vote_row: the row's variable and CSR range from one 8-B record and
-  // its successor instead of the cvar / crow arrays, one line per re-vote less): C2 25.94-26.00 vs 26.10-26.17
-  // ms, stress 28.83 vs 29.13 (same box).  LMMHIP_CREC=0: off.
-  P.crec = short_rows && env_int("LMMHIP_CREC", 1);
-  // Launch-width caps (tuning knobs, environment; 0 = uncapped): fewer blocks cut the fixed per-round
-  // cost of the grid-stride round kernels once the alive set is small.
-  const int cap_upd = env_int("LMMHIP_UPD_BLOCKS", 0);
+  // The mode (resolve_round_mode, lmm_round_mode.hpp), from the knobs' values:
+  // LMMHIP_CREC=0: no packed row records for the re-votes (vote_row: with them the row's variable and CSR range from
+  // one record instead of the cvar / crow arrays, one line per re-vote less): C2 25.94-26.00 vs 26.10-26.17 ms, stress
+  // 28.83 vs 29.13 (same box).
+  // LMMHIP_CMP_ROWS=0: the 8-B records and the compaction that copies the alive rows' elements, instead of the 16-B
+  // records {cvar, begin, end, 0}: a re-vote loads one record and reads its elements from the original CSR, and a
+  // compaction moves the per-row words only (cmp_count_rows / cmp_write_rows).
+  // LMMHIP_RDQ=0: the mm_ready pass.  Without it the update's workgroups (at most kMaxBlocks, each updating at most
+  // kUSeg constraints) list the ready constraints for the next round, the vote queues the ones it makes ready (C2
+  // 25.07-25.22 vs 25.34-25.39 ms, stress 28.29 vs 28.46, same box).
+  // LMMHIP_UPDQ_BLOCKS: those update workgroups, 4 per CU, each with a longer segment, so that the saturation's prefix
+  // over the segment counts is shorter — but enough of them to keep every segment within kUSeg.  Round 5, same box: C2
+  // 24.52-24.54 ms against 24.84-24.85 with one per 256 constraints (2,048 at C2), stress 27.86-27.94 vs 28.14; with
+  // the saturation cap at 5 per CU below, 24.41-24.45 (stress 27.75-27.77).
+  // LMMHIP_SATKEY=0: the state-read path.  Else the filter retires the rows of saturated targets on the key it gathered
+  // (kSatKey, vote_waves) and the re-votes read no variable state (the record forms of the short-row vote).
+  // LMMHIP_UPD_QUAD=0: mm_update moves a touched constraint's record lane by lane, in eight pieces, instead of one 64-B
+  // request per quad of lanes, both ways (update_groups, kQuad).
+  // LMMHIP_UPD_BLOCKS (launch-width cap, tuning knob; 0 = uncapped): fewer blocks cut the fixed per-round cost of the
+  // grid-stride update once the alive set is small.
+  RoundKnobs k;
+  k.crec = env_int("LMMHIP_CREC", 1);
+  k.rdq = env_int("LMMHIP_RDQ", 1);
+  k.satkey = env_int("LMMHIP_SATKEY", 1);
+  k.cmp_rows = env_int("LMMHIP_CMP_ROWS", 1);
+  k.upd_quad = env_int("LMMHIP_UPD_QUAD", 1);
+  k.upd_blocks = env_int("LMMHIP_UPD_BLOCKS", 0);
+  k.updq_blocks = env_int("LMMHIP_UPDQ_BLOCKS", updq_blocks_default(c->n_cu));
+  const RoundMode m = resolve_round_mode(c->group, d.nC, k, RoundLimits{kBlock, kUSeg, kMaxBlocks});
+  P.mode = m.vote;
+  P.upd_quad = m.upd_quad;
+  P.g_upd = m.g_upd;
   // the saturation's grid capped at 4 workgroups per CU (round 5, same box: C2 24.73-24.90 ms against 25.04-25.16
   // uncapped, i.e. up to kMaxBlocks = 2048; 768: 24.79-25.03, 1280: 24.76-24.81, 1536: 24.83-25.00, 512: 25.42-25.73;
   // stress 27.99-28.05 vs 28.29-28.36): every workgroup first rebuilds the prefix of the update's segment counts,
   // and half as many of them still give each ready constraint its waves
   // (with 4 update workgroups per CU: 5 per CU, 24.41-24.45 ms against 24.52-24.54 at 4 and 24.52-24.60 at 6 / 8)
   P.cap_sat = env_int("LMMHIP_SAT_BLOCKS", 5 * c->n_cu);
-  // ready constraints without the mm_ready pass: the update's workgroups (at most kMaxBlocks, each updating
-  // at most kUSeg constraints) list them for the next round, the vote queues the ones it makes ready (C2
-  // 25.07-25.22 vs 25.34-25.39 ms, stress 28.29 vs 28.46, same box; LMMHIP_RDQ=0: the mm_ready pass)
-  // (<= kMaxBlocks) Update workgroups: 4 per CU, each with a longer segment, so that the saturation's prefix over
-  // the segment counts is shorter — but enough of them to keep every segment within kUSeg (LMMHIP_UPDQ_BLOCKS).
-  // Round 5, same box: C2 24.52-24.54 ms against 24.84-24.85 with one per 256 constraints (2,048 at C2), stress
-  // 27.86-27.94 vs 28.14; with the saturation cap at 5 per CU below, 24.41-24.45 (stress 27.75-27.77)
-  const int64_t gU_need = (int64_t(d.nC) + kUSeg - 1) / kUSeg;
-  const int64_t gU_rdq = std::max<int64_t>(1, std::min<int64_t>(grid_for(d.nC, kBlock),
-      std::max<int64_t>(gU_need, env_int("LMMHIP_UPDQ_BLOCKS", 4 * c->n_cu))));
-  const int64_t per_blk = int64_t(kBlock) * ((int64_t(d.nC) + gU_rdq * kBlock - 1) / (gU_rdq * kBlock));
-  P.rdq = P.crec && env_int("LMMHIP_RDQ", 1) && per_blk <= kUSeg && cap_upd == 0;
-  // the filter retires the rows of saturated targets on the key it gathered (kSatKey, vote_waves) and the re-votes read
-  // no variable state (the row-record forms of the short-row vote).  LMMHIP_SATKEY=0: the state-read path
-  P.satkey = env_int("LMMHIP_SATKEY", 1) != 0;
-  // the 16-B row records {cvar, begin, end, 0}: a re-vote loads one record and reads its elements from the original
-  // CSR, and a compaction moves the per-row words only (cmp_count_rows / cmp_write_rows).  LMMHIP_CMP_ROWS=0: the 8-B
-  // records and the compaction that copies the alive rows' elements
-  P.rows = P.crec && env_int("LMMHIP_CMP_ROWS", 1) != 0;
-  const int row = short_rows ? (P.rdq ? 2 : P.crec ? 1 : 0) : c->group == 16 ? 3 : c->group == 32 ? 4 : 5;
-  const VoteKernels& vk = P.rows ? kVoteRowsTable[P.rdq][P.satkey] : kVoteTable[row][P.satkey];
+  const bool short_rows = c->group == 4 || c->group == 8;
+  const VoteKernels vk = short_rows ? kVoteTable[P.mode.index()]
+                                    : VoteKernels{nullptr, kVoteLong[c->group == 16 ? 0 : c->group == 32 ? 1 : 2]};
   // the LDS bitmap of changed constraints (one 1024-thread workgroup per CU); below LMMHIP_VOTE_BITS_ROWS alive rows
   // (host view, A/B knob; 0 = always) the change stamps gathered per row instead: no ~125-KB copy per CU
   // (LMMHIP_VOTE_BITS=0: always the stamps' path)
@@ -159,16 +160,11 @@ static RoundPlan round_plan(const lmmhip_ctx* c, const Dev& d) {
   // mm_saturate: waves per ready constraint and the grid's block cap (measurement knobs)
   const int sat_k = env_int("LMMHIP_SAT_WAVES", c->sat_waves);
   P.sat_waves = sat_k == 1 || sat_k == 2 ? sat_k : 4;
-  P.saturate = kSatTable[P.rdq][P.sat_waves == 4 ? 2 : P.sat_waves - 1];
+  P.saturate = kSatTable[P.mode.rdq()][P.sat_waves == 4 ? 2 : P.sat_waves - 1];
   P.sat_max = env_int("LMMHIP_SAT_GRID_MAX", kMaxBlocks);
-  // mm_update moves a touched constraint's record as one 64-B request per quad of lanes, both ways, instead of eight
-  // lane-by-lane pieces (update_groups, kQuad).  LMMHIP_UPD_QUAD=0: lane by lane
-  P.upd_quad = env_int("LMMHIP_UPD_QUAD", 1) != 0;
-  P.update = kUpdTable[P.rdq][P.upd_quad];
+  P.update = kUpdTable[m.upd().index()];
   P.g_init_c = grid_for(d.nC, kBlock / kWave);
   P.g_c = grid_for(d.nC, kBlock);
-  // mm_update: thread per constraint, identity order (ready-queue mode: at most kUSeg constraints per workgroup)
-  P.g_upd = P.rdq ? int(gU_rdq) : cap_upd > 0 && P.g_c > cap_upd ? cap_upd : P.g_c;
   // Compaction cadence (knobs): alive rows are re-counted every cmp_every rounds and rewritten when
   // fewer than cmp_pct % of the scanned rows are alive; the alive-constraint list every cl_every rounds.
   // Both decide and switch buffers on the device (ctl CTL_BUF / CTL_CB): no host round trip.
@@ -204,17 +200,16 @@ static RoundPlan round_plan(const lmmhip_ctx* c, const Dev& d) {
 
 // The plan's buffers, into the solve's own Dev: the context's never carries them (lmm_dev.hpp), so no other engine —
 // whose compactions do not maintain the row records — ever sees them.
-// (cmpbits: the compaction's alive bits, 16-B-record mode only — an argument of its two kernels, not part of the Dev)
+// (cmpbits: the compaction's alive bits, RowForm::Rec16 only — an argument of its two kernels, not part of the Dev)
 static int round_buffers(lmmhip_ctx* c, Dev& d, const RoundPlan& P, uint8_t** cmpbits) {
-  if (P.crec)
-    for (int k = 0; k < 3; k++)
-      if (int rc = P.rows ? scratch(c, c->rounds.crec[k], int64_t(d.nV) + 1, &d.crec[k].r16)
-                          : scratch(c, c->rounds.crec[k], int64_t(d.nV) + 1, &d.crec[k].r8))
-        return rc;
-  if (P.rows)
+  for (int k = 0; k < 3 && P.mode.rec(); k++)  // (the member of RowRecs the RowForm selects)
+    if (int rc = P.mode.rec16() ? scratch(c, c->rounds.crec[k], int64_t(d.nV) + 1, &d.crec[k].r16)
+                                : scratch(c, c->rounds.crec[k], int64_t(d.nV) + 1, &d.crec[k].r8))
+      return rc;
+  if (P.mode.rec16())
     if (int rc = scratch(c, c->rounds.cmpbits, (int64_t(d.nV) + kCompactRows - 1) / kCompactRows * kBlock, cmpbits))
       return rc;
-  if (P.rdq) {
+  if (P.mode.rdq()) {
     const int64_t n = std::max<int64_t>(d.nC, 1);
     if (int rc = scratch(c, c->rounds.rdq[0], n, &d.rdq[0]) | scratch(c, c->rounds.rdq[1], n, &d.rdq[1]) |
                  scratch(c, c->rounds.rqst, n, &d.rqst) | scratch(c, c->rounds.useg, int64_t(P.g_upd) * kUSeg, &d.useg) |
@@ -231,8 +226,8 @@ static int round_buffers(lmmhip_ctx* c, Dev& d, const RoundPlan& P, uint8_t** cm
 static int launch_vote(lmmhip_ctx* c, const Dev& d, const RoundPlan& P, int64_t r, int64_t nrows) {
   const bool bitmap = P.vote_bitmap && nrows >= P.vote_bits_rows;
   if (bitmap && c->profiling && c->vote_diag) {  // measurement: bitmap load alone, filter alone (slot 7)
-    LAUNCH(7, r + 1000000, (mm_vote_lane<kVBlock, true, 2>), c->n_cu, kVBlock, d, int(r));
-    LAUNCH(7, r, (mm_vote_lane<kVBlock, true, 1>), c->n_cu, kVBlock, d, int(r));
+    LAUNCH(7, r + 1000000, (mm_vote_lane<VoteForm::Bitmap, kVoteArrays, 2>), c->n_cu, kVBlock, d, int(r));
+    LAUNCH(7, r, (mm_vote_lane<VoteForm::Bitmap, kVoteArrays, 1>), c->n_cu, kVBlock, d, int(r));
     LAUNCH(7, r, mm_vote_diagcount, grid_for((int64_t(d.nC) + 63) / 64, kBlock), kBlock, d, int(r));
   }
   LAUNCH(2, r, bitmap ? P.vote_bitmap : P.vote_scan, bitmap ? c->n_cu : grid_for(nrows, kBlock), bitmap ? kVBlock : kBlock,
@@ -250,7 +245,7 @@ int solve_maxmin(lmmhip_ctx* c, double prec) {
   if (int rc = round_buffers(c, d, P, &cmpbits))
     return rc;
   LAUNCH(0, -1, mm_init_cnsts, P.g_init_c, kBlock, d, prec);
-  LAUNCH(1, -1, mm_init_vars, grid_for(d.nV, kBlock), kBlock, d, int(P.rows));
+  LAUNCH(1, -1, mm_init_vars, grid_for(d.nV, kBlock), kBlock, d, int(P.mode.rec16()));
   LAUNCH(1, -1, mm_clist, std::min(P.g_c, 2 * c->n_cu), kBlock, d, 1);
   HIPCHK(hipMemsetAsync(d.chgbits, 0, sizeof(uint64_t) * ((d.nC + 127) / 128 * 2 + 2), c->stream));
   // Host view of the sizes (upper bounds: rows and constraints only leave), refreshed at every poll; they
@@ -260,11 +255,11 @@ int solve_maxmin(lmmhip_ctx* c, double prec) {
     if (int rc = launch_vote(c, d, P, r, nrows))
       return rc;
     const int gL = grid_for(ncl, kBlock);
-    if (!P.rdq)  // (ready-queue mode: no mm_ready pass, the update's segments — g_upd of them — and the vote's queue)
+    if (!P.mode.rdq())  // (ready-queue mode: no mm_ready pass, the update's segments — g_upd of them — and the vote's queue)
       LAUNCH(3, r, mm_ready, gL, kBlock, d);
     const int64_t gS = std::max<int64_t>(1, std::min<int64_t>((P.sat_waves * ncl + kBlock - 1) / kBlock, P.sat_max));
     LAUNCH(4, r, P.saturate, int(P.cap_sat > 0 && gS > P.cap_sat ? P.cap_sat : gS), kBlock, d, int(r),
-           P.rdq ? P.g_upd : gL);
+           P.mode.rdq() ? P.g_upd : gL);
     LAUNCH(5, r, P.update, P.g_upd, kBlock, d, int(r), prec);
     return 0;
   };
@@ -281,14 +276,18 @@ int solve_maxmin(lmmhip_ctx* c, double prec) {
     }
     if (r - last_compact >= P.cmp_every && nrows > 4096) {  // order-preserving compaction of the alive rows
       const int nblk = int((nrows + kCompactRows - 1) / kCompactRows);
-      if (P.rows) {
-        LAUNCH(6, r, cmp_count_rows, nblk, kBlock, d, cmpbits);
-        LAUNCH(6, r, cmp_scan<true>, 1, 1024, d, nblk, P.cmp_pct);
-        LAUNCH(6, r, cmp_write_rows, nblk, kBlock, d, cmpbits);
-      } else {
-        LAUNCH(6, r, cmp_count, nblk, kBlock, d);
-        LAUNCH(6, r, cmp_scan<false>, 1, 1024, d, nblk, P.cmp_pct);
-        LAUNCH(6, r, cmp_write, nblk, kBlock, d);
+      switch (P.mode.form) {
+        case RowForm::Rec16:  // the per-row words only
+          LAUNCH(6, r, cmp_count_rows, nblk, kBlock, d, cmpbits);
+          LAUNCH(6, r, cmp_scan<true>, 1, 1024, d, nblk, P.cmp_pct);
+          LAUNCH(6, r, cmp_write_rows, nblk, kBlock, d, cmpbits);
+          break;
+        case RowForm::Arrays:
+        case RowForm::Rec8:  // rows and elements (and the 8-B records where the solve has them)
+          LAUNCH(6, r, cmp_count, nblk, kBlock, d);
+          LAUNCH(6, r, cmp_scan<false>, 1, 1024, d, nblk, P.cmp_pct);
+          LAUNCH(6, r, cmp_write, nblk, kBlock, d);
+          break;
       }
       last_compact = r;
       cm = true;

@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "lmm_dev.hpp"
+#include "lmm_round_mode.hpp"
 
 namespace lmmdev {
 
@@ -97,9 +98,9 @@ __global__ void __launch_bounds__(kBlock) mm_init_cnsts(Dev s, double prec) {
   init_cnsts_waves(s, prec, wave, int64_t(gridDim.x) * (kBlock / kWave));
 }
 
-// kRec: also the packed row records of buffer 0 (the multi-launch engine's init only); kRow: in their 16-B form
-// {cvar, begin, end, 0} (RowRecs::r16).
-template <bool kRec = false, bool kRow = false>
+// F: also the packed row records of buffer 0 in that form (the multi-launch engine's init only; Rec8: where the solve
+// has them — the Arrays mode runs this instantiation too, its records null).
+template <RowForm F>
 __device__ __forceinline__ void init_vars_range(const Dev& s, int64_t t, int64_t nthreads) {
   for (int64_t v = t; v < s.nV; v += nthreads) {
     s.x[v] = 0.0;
@@ -107,24 +108,25 @@ __device__ __forceinline__ void init_vars_range(const Dev& s, int64_t t, int64_t
     s.rtgt[0][v] = kUnvoted;
     const int32_t cv = int32_t(v) | (s.vbound[v] > 0 ? int32_t(0x80000000u) : 0);
     const_cast<int32_t*>(s.cvar[0])[v] = cv;
-    if (kRec && kRow)
+    if (F == RowForm::Rec16)
       s.crec[0].r16[v] = make_uint4(uint32_t(cv), s.var_ptr[v], s.var_ptr[v + 1], 0u);
-    else if (kRec && s.crec[0].r8)
+    else if (F == RowForm::Rec8 && s.crec[0].r8)
       s.crec[0].r8[v] = make_uint2(uint32_t(cv), s.var_ptr[v]);
   }
 }
 
-// rows: the records are the 16-B ones, which need no sentinel behind the last row.
-__global__ void __launch_bounds__(kBlock) mm_init_vars(Dev s, int rows) {
+// rec16: the solve's RowForm is Rec16, whose records need no sentinel behind the last row.  (An int, not the RowForm: a
+// compare with Rec16 instead of with zero is another instruction, and the mode types came in without moving any.)
+__global__ void __launch_bounds__(kBlock) mm_init_vars(Dev s, int rec16) {
   const int64_t t = int64_t(blockIdx.x) * kBlock + threadIdx.x, nthreads = int64_t(gridDim.x) * kBlock;
-  if (rows)
-    init_vars_range<true, true>(s, t, nthreads);
+  if (rec16)
+    init_vars_range<RowForm::Rec16>(s, t, nthreads);
   else
-    init_vars_range<true>(s, t, nthreads);
+    init_vars_range<RowForm::Rec8>(s, t, nthreads);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     s.ctl[CTL_NROWS + 0] = s.nV;
     s.ctl[CTL_NELEM + 0] = int32_t(s.nnz);
-    if (!rows && s.crec[0].r8)
+    if (!rec16 && s.crec[0].r8)
       s.crec[0].r8[s.nV] = make_uint2(0u, s.var_ptr[s.nV]);
   }
 }
@@ -449,37 +451,39 @@ constexpr int kFilt = LMM_KFILT;  // rows per lane per filter step (their loads 
 
 // Re-vote of one row, one lane: the first R elements in registers (their loads in flight together), longer
 // rows loop over the rest.  Every load indexed by the row or its variable is issued at once.
-// kRec: the row's variable and CSR range from the packed records (crec; the multi-launch engine's short-row
-// vote only — other instantiations, e.g. the persistent kernel, keep their register budget).
+// M (the vote mode's index, lmm_round_mode.hpp) — rec(): the row's variable and CSR range from the packed records (crec;
+// the multi-launch engine's short-row vote only — the Arrays mode, e.g. the persistent kernel, keeps its register budget).
 // (an: the dependent levels into lv[0..5]: row record, variable state, row elements, keys, exact ratios, the vote's
 // stores and atomics)
-// kRdq: a constraint this re-vote made ready (nothing votes elsewhere any more) is returned in *rdq_c for the
+// rdq(): a constraint this re-vote made ready (nothing votes elsewhere any more) is returned in *rdq_c for the
 // caller's workgroup-wide queueing (rdq_push_lds), or queued here when rdq_c is null.
-// kSat: the caller's filter retires the rows of saturated targets itself (vote_waves, kSatRet), so a row that has
+// sat_retire(): the caller's filter retires the rows of saturated targets itself (vote_waves), so a row that has
 // voted before and reaches here has an alive variable: its state is not read.  Only a row that never voted
 // (kUnvoted) still reads it.
-// kRow (with kRec): the records are the 16-B ones {cvar, begin, end, 0}, one load, and the row's elements are read
+// rec16(): the records are the 16-B ones {cvar, begin, end, 0}, one load, and the row's elements are read
 // from the original CSR whatever the buffer (the compaction moves the per-row words only, cmp_write_rows).
-template <int R, bool kRec = false, bool kRdq = false, bool kSat = false, bool kRow = false>
+template <int R, int M>
 __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64_t row, int* st_rows,
                                          int* st_elems, const uint16_t* __restrict__ key, int* rdq_c = nullptr,
                                          Anat an = Anat()) {
+  static_assert(vote_mode_ok(M), "not one of the nine vote modes");
+  constexpr VoteMode vm = vote_mode(M);
   an.restart();
   const int32_t* __restrict__ cvar = s.cvar[buf];
   const uint32_t* __restrict__ crow = s.crow[buf];
-  const int32_t* __restrict__ ccol = s.ccol[kRow ? 0 : buf];
+  const int32_t* __restrict__ ccol = s.ccol[vm.rec16() ? 0 : buf];
   int32_t* __restrict__ rtgt = s.rtgt[buf];
   uint16_t* __restrict__ skey = s.skey[buf];
   // (key: s.key, or its copy in LDS — persistent engine, small systems)
   const int t = rtgt[row];
   int32_t cv;
   uint32_t b, e;
-  if (kRec && kRow) {
+  if (vm.rec16()) {
     const uint4 r = s.crec[buf].r16[row];
     cv = int32_t(r.x);
     b = r.y;
     e = r.z;
-  } else if (kRec) {  // (the row's variable and CSR range from one 8-B record and its successor)
+  } else if (vm.rec()) {  // (the row's variable and CSR range from one 8-B record and its successor)
     const uint2 r0 = s.crec[buf].r8[row], r1 = s.crec[buf].r8[row + 1];
     cv = int32_t(r0.x);
     b = r0.y;
@@ -491,7 +495,7 @@ __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64
   }
   an.level(0, b + e + uint32_t(t) + uint32_t(cv));
   const int v = rvar(cv);
-  const int32_t vst = !kSat || t == kUnvoted ? s.vstate[v] : 0;
+  const int32_t vst = !vm.sat_retire() || t == kUnvoted ? s.vstate[v] : 0;
   const bool bnd = rbounded(cv);
   const double vb = bnd ? s.vbound[v] : -1.0;
   const double p = bnd ? s.pen[v] : 1.0;  // read below only when vb > 0
@@ -559,9 +563,9 @@ __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64
   if (nmin > 1 || vb > 0) {  // exact ratios at the minimal key: lexicographic min of (ratio, id)
     newt = INT_MAX;
     // the tied constraints' ratios: all loads issued before the first compare (one dependent level: a compare right
-    // after each conditional load waits for the loads one at a time).  Not in the persistent kernel (kRec = kRdq =
-    // false), whose 128-VGPR budget the ratios array exceeds (47 VGPRs spilled).
-    constexpr bool kTieLd = kRec || kRdq;
+    // after each conditional load waits for the loads one at a time).  Not in the Arrays mode: the persistent
+    // kernel's 128-VGPR budget the ratios array exceeds (47 VGPRs spilled).
+    constexpr bool kTieLd = vm.tie_loads();
     double rr[kTieLd ? R : 1];
     if (kTieLd) {
 #pragma unroll
@@ -620,7 +624,7 @@ __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64
     return;
   if (t >= 0 && !key_dead(kt))
     atomicAdd(&s.nvote[t], mult_old);
-  if (kRdq) {
+  if (vm.rdq()) {
     const int old = atomicSub(&s.nvote[newt], mult_new);
     if (old == mult_new) {  // nothing votes elsewhere any more: ready
       if (rdq_c)
@@ -647,11 +651,11 @@ __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64
 // target was touched at all (chg stamp).  Returns the rows this wave queued (lane-uniform).
 // kDiag (measurement only, LMMHIP_VOTE_DIAG): 1 = the filter alone (rows queued, none resolved), with
 // per-round counters of target-changed / sensitive / queued rows in vstat's kDiagSlot.
-// kSatRet: a row whose target saturated last round (its gathered key is kSatKey) is not queued: its variable was fixed
-// by that saturation — a constraint saturates only when every alive element on it votes for it, and claims every alive
-// variable on it, so "the row's target saturated" and "the row's variable was fixed by a saturation" are one event —
-// and the lane stores kRetired itself.  The re-votes (vote_row, kSat) then read no variable state.  The diagnostic
-// filter (kDiag 1) stays read-only and counts such rows in word 7 of its record (they are part of its queued count).
+// M (the vote mode), sat_retire(): a row whose target saturated last round (its gathered key is kSatKey) is not queued:
+// its variable was fixed by that saturation — a constraint saturates only when every alive element on it votes for it,
+// and claims every alive variable on it, so "the row's target saturated" and "the row's variable was fixed by a
+// saturation" are one event — and the lane stores kRetired itself.  The re-votes (vote_row) then read no variable state.
+// The diagnostic filter (kDiag 1) stays read-only and counts such rows in word 7 of its record (part of its queued count).
 constexpr int kQW = 2 * kWave;  // per-wave queue capacity
 
 // The wave's row range [wlo, whi) of the workgroup's rows [lo, hi).
@@ -665,12 +669,12 @@ __device__ __forceinline__ void vote_wave_range(int64_t lo, int64_t hi, int64_t&
 
 // an: the filter steps and re-vote batches of this wave (lv[6] filter loads, lv[7] filter gathers, lv[8] re-vote
 // batches; counters 0 steps, 1 batches); ar: vote_row's levels.
-template <bool kBits, int R, int F, int kDiag, bool kRec = false, bool kRdq = false, bool kSatRet = false,
-          bool kRow = false>
+template <bool kBits, int R, int F, int kDiag, int M>
 __device__ __forceinline__ int vote_waves(const Dev& s, int buf, int round, int64_t lo, int64_t hi,
                                           const uint64_t* bits, int* qw, int* st_rows, int* st_elems,
                                           const uint16_t* __restrict__ key, RdqLds* rql = nullptr, Anat an = Anat(),
                                           Anat ar = Anat()) {
+  constexpr VoteMode vm = vote_mode(M);
   const int lane = threadIdx.x & (kWave - 1);
   int64_t wlo, whi;
   vote_wave_range(lo, hi, wlo, whi);
@@ -728,7 +732,7 @@ __device__ __forceinline__ int vote_waves(const Dev& s, int buf, int round, int6
         need = key_dead(kt[u]) || !(kt[u] < sk[u]);
       else if (kBits && cg[u] == prev)
         need = true;
-      if (kSatRet && kDiag == 0 && ch[u] && kt[u] == kSatKey) {  // fixed with its target: retired here
+      if (vm.sat_retire() && kDiag == 0 && ch[u] && kt[u] == kSatKey) {  // fixed with its target: retired here
         s.rtgt[buf][base + u * kWave + lane] = kRetired;
         need = false;
       }
@@ -757,12 +761,12 @@ __device__ __forceinline__ int vote_waves(const Dev& s, int buf, int round, int6
         nq += kWave;
         const int row = qw[qn + lane];
         __builtin_amdgcn_wave_barrier();
-        int pc = -1;  // (kRdq) a constraint this lane's re-vote made ready
+        int pc = -1;  // (rdq()) a constraint this lane's re-vote made ready
         an.restart();
         an.count(1);
         if (kDiag == 0)
-          vote_row<R, kRec, kRdq, kSatRet, kRow>(s, buf, round, row, st_rows, st_elems, key, &pc, ar);
-        if (kRdq && kDiag == 0)
+          vote_row<R, M>(s, buf, round, row, st_rows, st_elems, key, &pc, ar);
+        if (vm.rdq() && kDiag == 0)
           rdq_push_lds(s, pc, round, rql);
         an.level(8, 0u);
       }
@@ -775,8 +779,8 @@ __device__ __forceinline__ int vote_waves(const Dev& s, int buf, int round, int6
   }
   int pc = -1;
   if (kDiag == 0 && lane < qn)
-    vote_row<R, kRec, kRdq, kSatRet, kRow>(s, buf, round, qw[lane], st_rows, st_elems, key, &pc, ar);
-  if (kRdq && kDiag == 0)
+    vote_row<R, M>(s, buf, round, qw[lane], st_rows, st_elems, key, &pc, ar);
+  if (vm.rdq() && kDiag == 0)
     rdq_push_lds(s, pc, round, rql);
   if (an.on() && qn > 0)
     an.level(8, 0u);
@@ -855,13 +859,15 @@ __global__ void __launch_bounds__(kBlock) mm_vote_diagcount(Dev s, int round) {
 }
 
 // Multi-launch engine, short rows (mean length <= 8): one 1024-thread workgroup per CU (the bitmap takes up
-// to kBitWords * 8 B of LDS), one contiguous chunk of rows per workgroup.
-constexpr int kVBlock = 1024;
+// to kBitWords * 8 B of LDS), one contiguous chunk of rows per workgroup.  V: that form or the scan form (workgroup size
+// and LDS bitmap together); M: the vote mode's index.
+constexpr int kVBlock = vote_block(VoteForm::Bitmap);
 // (Round 5 measured the first filter step's loads issued before the bitmap copy: 24.313 / 24.390 ms against 24.340 /
 // 24.309 without, profiles/r05_ab_c2_spec2.json — neutral, the copy is not the vote's critical path; removed.)
-template <int B, bool kBits, int kDiag = 0, bool kRec = false, bool kRdq = false, bool kSatRet = false,
-          bool kRow = false>
-__global__ void __launch_bounds__(B) mm_vote_lane(Dev s, int round) {
+template <VoteForm V, int M, int kDiag = 0>
+__global__ void __launch_bounds__(vote_block(V)) mm_vote_lane(Dev s, int round) {
+  constexpr int B = vote_block(V);
+  constexpr bool kBits = vote_bits(V), kRdq = vote_mode(M).rdq();
   AnatWave aw, awr;  // (the wave's filter steps and batches; vote_row's levels)
   const Anat an = kDiag == 0 ? aw.open(s, round, ANAT_VOTE) : Anat();
   const Anat ar = kDiag == 0 ? awr.open(s, round, ANAT_VOTE) : Anat();
@@ -898,9 +904,8 @@ __global__ void __launch_bounds__(B) mm_vote_lane(Dev s, int round) {
   }
   int nq = 0;
   if (lo < hi)
-    nq = vote_waves<kBits, 8, kFilt, kDiag, kRec, kRdq, kSatRet, kRow>(s, buf, round, lo, hi, bits,
-                                                                       q + (threadIdx.x / kWave) * kQW, &st_rows,
-                                                                       &st_elems, s.key, &rql, an, ar);
+    nq = vote_waves<kBits, 8, kFilt, kDiag, M>(s, buf, round, lo, hi, bits, q + (threadIdx.x / kWave) * kQW, &st_rows,
+                                               &st_elems, s.key, &rql, an, ar);
   if (kRdq && kDiag == 0)
     rdq_flush_lds(s, round, &rql);
   if (an.on()) {  // the wave's record (vote_row's levels: the slowest lane of the wave)
@@ -1470,10 +1475,12 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-template <int K, bool kRdq = false, bool kQuad = false>
+template <int K, int U>  // U: the update mode's index (lmm_round_mode.hpp)
 __device__ __forceinline__ int update_groups(const Dev& s, int64_t wbase, int64_t stride, int round, double prec,
                                              bool* touch, int* ucnt_sh = nullptr, int32_t* ulist = nullptr,
                                              Anat an = Anat(), UpdQuadLds<K>* ql = nullptr) {
+  static_assert(upd_mode_ok(U), "not an update mode");
+  constexpr bool kRdq = upd_mode(U).rdq(), kQuad = upd_mode(U).quad();
   const int lane = threadIdx.x & (kWave - 1);
   // (kQuad: the wave's base as the scalar it is — the groups' addresses are then a scalar base and a 32-bit lane
   // offset instead of 64-bit registers per array and group, which the quad pieces' registers leave no room for)
@@ -1728,8 +1735,9 @@ __device__ __forceinline__ int update_groups(const Dev& s, int64_t wbase, int64_
 #define LMM_UPD_K 4
 #endif
 // kQuad: the touched records move as one 64-B request per quad (update_groups; LMMHIP_UPD_QUAD, the default).
-template <bool kRdq = false, bool kQuad = false>
-__global__ void __launch_bounds__(kBlock, kQuad ? 4 : 1) mm_update(Dev s, int round, double prec) {
+template <int U>
+__global__ void __launch_bounds__(kBlock, upd_mode(U).quad() ? 4 : 1) mm_update(Dev s, int round, double prec) {
+  constexpr bool kRdq = upd_mode(U).rdq(), kQuad = upd_mode(U).quad();
   AnatWave aw;
   const Anat an = aw.open(s, round, ANAT_UPD);
   const unsigned long long t_in = an.now();
@@ -1752,7 +1760,7 @@ __global__ void __launch_bounds__(kBlock, kQuad ? 4 : 1) mm_update(Dev s, int ro
   const int64_t stride = int64_t(gridDim.x) * kBlock;
   for (int64_t base = (int64_t(blockIdx.x) * kBlock + threadIdx.x) & ~int64_t(kWave - 1); base < s.nC;
        base += LMM_UPD_K * stride)  // wave-uniform; LMM_UPD_K groups of 64 constraints per step, loads in flight together
-    alive += update_groups<LMM_UPD_K, kRdq, kQuad>(s, base, stride, round, prec, &any_touch, &ucnt_sh, ulist, an, ql);
+    alive += update_groups<LMM_UPD_K, U>(s, base, stride, round, prec, &any_touch, &ucnt_sh, ulist, an, ql);
   const unsigned long long t_loop = an.now();
   if (alive)
     atomicAdd(&alive_cnt, alive);

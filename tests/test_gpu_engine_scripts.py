@@ -168,6 +168,47 @@ def test_round_engine_variants_on_scripts(shape, variant, compact, monkeypatch):
         assert _launches(d.s)[6] >= base.launches6 + 4, (env, _launches(d.s)[6], base.launches6)
 
 
+# ---- every mode of the round engine (simgrid_amd/csrc/lmm_round_mode.hpp) --------------------------------------------
+# the nine vote modes by their knobs: (name, LMMHIP_CREC, LMMHIP_CMP_ROWS, LMMHIP_RDQ, LMMHIP_SATKEY); without row records
+# (Arrays) the queue and the filter do not exist, whatever their knobs say
+ROUND_MODES = [("Arrays", "0", "1", "1", "1")]
+ROUND_MODES += [(f"{form}-q{q}-f{f}", "1", rows, q, f)
+                for form, rows in (("Rec8", "0"), ("Rec16", "1")) for q in "01" for f in "01"]
+MODE_KNOBS = ("LMMHIP_CREC", "LMMHIP_CMP_ROWS", "LMMHIP_RDQ", "LMMHIP_SATKEY")
+# (mode, forced compactions): every mode below the compaction threshold; above it, under COMPACT, the three row forms
+# x the queue — there the records and the two compaction families matter
+MODE_CASES = [(m, False) for m in ROUND_MODES]
+MODE_CASES += [(("Arrays-q1", "0", "1", "1", "1"), True), (("Arrays-q0", "0", "1", "0", "1"), True)]
+MODE_CASES += [(m, True) for m in ROUND_MODES[1:] if m[0].endswith("f1")]
+
+
+@pytest.mark.parametrize("mode,compact", MODE_CASES, ids=[m[0] + ("-compact" if c else "") for m, c in MODE_CASES])
+def test_every_round_mode_matches_the_default(mode, compact, monkeypatch):
+    """Each of the nine vote modes, in both forms of the lane vote (LMMHIP_VOTE_BITS 1, 0) and both update paths
+    (LMMHIP_UPD_QUAD 1, 0), on R4 seed 0 (below the 4096 rows under which nothing compacts); and the three row forms x
+    the ready queue on R4L seed 1 with the compactions forced.  Every solve gives the default's bytes, round count,
+    per-variable rounds and saturated set, and the default meets the oracle.  The mm_ready pass (slot 3) is launched
+    exactly when the mode has no ready queue: the one way a test sees which family of kernels ran."""
+    shape, seed = ("R4L", 1) if compact else ("R4", 0)
+    for k in MODE_KNOBS + ("LMMHIP_VOTE_BITS", "LMMHIP_UPD_QUAD", "LMMHIP_UPD_BLOCKS", "LMMHIP_UPDQ_BLOCKS") + tuple(COMPACT):
+        monkeypatch.delenv(k, raising=False)
+    base = rounds_solved(shape, seed)
+    assert base.rounds > 2 and np.count_nonzero(base.x) > 0
+    assert_matches_oracle(base, *oracle_solved(shape, seed), shape)
+    name, crec = mode[0], mode[1]
+    queue = crec == "1" and mode[3] == "1"
+    for bits, quad in (("1", "1"),) if compact else itertools.product("10", "10"):
+        env = dict(zip(MODE_KNOBS, mode[1:]), LMMHIP_VOTE_BITS=bits, LMMHIP_UPD_QUAD=quad, **(COMPACT if compact else {}))
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        d = Solved(K.engine_script(shape, seed), "rounds")
+        assert_same_solve(base, d, (name, env))
+        n = _launches(d.s)
+        assert n[2] > 0 and n[5] > 0 and (n[3] == 0) == queue, (name, env, n)
+        if compact:  # (as in test_round_engine_variants_on_scripts: at least one whole row compaction and the switch)
+            assert n[6] >= base.launches6 + 4, (name, env, n[6], base.launches6)
+
+
 # ---- the launch sequence of the two round-chain engines ----------------------------------------------------------------
 # (shape, engine, forced compactions): the small shapes are below the 4096 rows / constraints under which nothing
 # compacts, the L ones are the smallest above them; the frontier engine has no compaction knobs
