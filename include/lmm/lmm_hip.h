@@ -167,11 +167,29 @@ int lmmhip_get_var_rounds(lmmhip_ctx* ctx, int32_t* rounds_out);
  *           leaves behind (maxmin.cpp:397-409), recomputed the way SURVEY.md A.6 compares it;
  *   FAIR_BOTTLENECK: c was erased (remaining <= 0, fair_bottleneck.cpp:129-140). */
 int lmmhip_get_saturated(lmmhip_ctx* ctx, uint8_t* saturated_out);
+/* Usage of every constraint of the solved system (n_cnst doubles, dense order), computed on the device from the
+ * values in HBM: U_c = Constraint::get_usage() (maxmin.cpp:948-961), the sum (FATPIPE: the max) of weight * value
+ * over the constraint's flattened elements; 0 for a constraint without one.  After a solve of either kind and by
+ * any engine.  It is the number lmmhip_get_saturated's MAXMIN test is decided from (one device function computes
+ * both), a fixed function of the constraint's element segment and the values: two calls give the same bytes.
+ * Errors as lmmhip_get_saturated: LMMHIP_E_STATE without a solved system, LMMHIP_E_ARG for a null output with
+ * n_cnst > 0. */
+int lmmhip_get_usage(lmmhip_ctx* ctx, double* usage_out);
+/* The same usages left in device memory, for device-resident consumers (the companion of
+ * lmmhip_values_device_ptr): queues the pass on the context's current stream and returns the pointer of the
+ * context-owned buffer without synchronising the host; work queued on that stream afterwards sees the usages.
+ * Valid until the next upload, flatten, solve or usage call on the context. */
+int lmmhip_usage_device_ptr(lmmhip_ctx* ctx, const double** dptr);
 /* Variables the last flatten put in the system — the Lazy models' modified_set_ side effect of the
  * solve (every variable of an active element of a listed constraint, maxmin.cpp:536-538) — in the
  * caller's id space: dense CSR indices after lmmhip_upload, host variable slots after
  * lmmhip_res_flatten (ascending).  *n = count; ids == NULL = size query; cap must be >= *n. */
 int lmmhip_get_touched_vars(lmmhip_ctx* ctx, int32_t* ids, int64_t cap, int64_t* n);
+/* The constraint-side twin: the constraints of the flattened system in the caller's id space, ids[d] = the id of
+ * dense constraint d (the order of lmmhip_get_usage and lmmhip_get_saturated): the dense indices themselves after
+ * lmmhip_upload, host constraint slots after lmmhip_res_flatten / lmmhip_res_flatten_fair (the listed constraints
+ * that hold a member element, in list order).  *n = count; ids == NULL = size query; cap must be >= *n. */
+int lmmhip_get_touched_cnsts(lmmhip_ctx* ctx, int32_t* ids, int64_t cap, int64_t* n);
 /* Connected components of the uploaded (or resident-flattened) system's variable-constraint graph — the
  * closure System::update_modified_set walks from one constraint (maxmin.cpp:898-922), for every component at
  * once (components spread over GPUs).  Lock-free union-find on the device; component ids

@@ -127,6 +127,26 @@ int lmm_flat_export(lmm_sys* s, int64_t* counts3, int64_t* var_ptr, int32_t* cns
  * order for a FairBottleneck system (the order its per-element chain subtracts in, fair_bottleneck.cpp:
  * 111-116), ascending CSR order for a max-min one.  nnz must equal lmm_flat_export's count. */
 int lmm_flat_export_order(lmm_sys* s, int64_t nnz, int64_t* csc_order);
+/* The constraints of that flattened system: cnst_ids[d] = the constraint id of dense constraint d (the order of
+ * lmm_flat_export's cbound / cflags; cnst_idx holds these dense indices).  cap must be >= lmm_flat_export's n_cnst.
+ * Host only, and the same flatten as lmm_flat_export (with its side effects). */
+int lmm_flat_export_cnsts(lmm_sys* s, int64_t* cnst_ids, int64_t cap);
+/* Constraint usage of the last device solve, computed on the device from the values in HBM (lmmhip_get_usage: the
+ * reduction the device's saturated set is decided from), so it needs no lmm_fetch: valid after lmm_device_solve
+ * (and after lmm_solve / lmm_lmm_solve, which end with the fetch), in resident mode or not, selective or not, for
+ * max-min and FairBottleneck.  Returns the count n of the solved (flattened) system's constraints and fills
+ * cnst_ids[d] / usage[d], d = dense order (cap >= n); null arrays = size query; -1 with lmm_last_error() before
+ * any device solve of the system (or after lmm_solve_batch, whose context holds the union).
+ *   - The flattened system holds the listed constraints (the active set; the modified set in selective mode) on
+ *     which a member variable has an enabled element of weight > 0.
+ *   - A listed constraint that is not flattened has only variables the solve reset to 0: its usage is 0, and it is
+ *     not returned.
+ *   - A constraint outside the solve list (selective mode) is not returned either: its usage is what
+ *     lmm_constraint_get_usage gives on the host.
+ * Nothing is remembered per constraint between solves: a constraint that goes inactive leaves every list without
+ * being solved again, so the answer always describes the last solve only.  lmm_constraint_get_usage (the host
+ * walk over the fetched values) is unchanged. */
+int64_t lmm_device_usage(lmm_sys* s, int64_t* cnst_ids, double* usage, int64_t cap);
 /* Solve n independent systems as one device launch sequence (disjoint union). */
 int lmm_solve_batch(lmm_sys** systems, int n);
 

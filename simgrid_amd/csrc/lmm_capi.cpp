@@ -389,6 +389,31 @@ int lmm_flat_export_order(lmm_sys* s, int64_t nnz, int64_t* csc_order) {
   }
 }
 
+int lmm_flat_export_cnsts(lmm_sys* s, int64_t* cnst_ids, int64_t cap) {
+  try {
+    System::Flat f;
+    s->sys.flatten_into(f);
+    if (int64_t(f.dense_cnsts.size()) > cap || (!cnst_ids && !f.dense_cnsts.empty())) {
+      g_err = "lmm_flat_export_cnsts: cap is below the flattened system's constraint count";
+      return -1;
+    }
+    std::copy(f.dense_cnsts.begin(), f.dense_cnsts.end(), cnst_ids);
+    return 0;
+  } catch (const std::exception& ex) {
+    g_err = ex.what();
+    return -1;
+  }
+}
+
+int64_t lmm_device_usage(lmm_sys* s, int64_t* cnst_ids, double* usage, int64_t cap) {
+  try {
+    return s->sys.device_usage(cnst_ids, usage, cap);
+  } catch (const std::exception& ex) {
+    g_err = ex.what();
+    return -1;
+  }
+}
+
 int lmm_solve_batch(lmm_sys** systems, int n) {
   try {
     std::vector<System*> v(size_t(n > 0 ? n : 0));

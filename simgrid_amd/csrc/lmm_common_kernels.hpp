@@ -64,10 +64,25 @@ __global__ void mm_ctl_out(Dev s, int32_t* dst) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
 }
 
+// U_c = Constraint::get_usage() of constraint c from the solved values (maxmin.cpp:948-961: sum, or max for
+// FATPIPE, of w * x over the enabled elements of weight > 0 — exactly the flattened CSC of c), by one whole wave
+// (every lane calls it with the same c): lane l takes the elements l, l + 64, ... of the segment in order, then the
+// butterfly of wave_sum / wave_max, so every lane returns the same U_c.  A fixed function of the segment and x: no
+// atomics, nothing of the grid.  Reads x, csc_w, csc_v, cnst_ptr and cflags only, which every engine of either
+// solver leaves valid.  Both the saturated set and the usage the caller reads come from here.
+__device__ __forceinline__ double cnst_usage_wave(const Dev& s, int64_t c, int lane) {
+  const bool fat = s.cflags[c] & 1;
+  double u = 0.0;
+  for (uint32_t j = s.cnst_ptr[c] + lane; j < s.cnst_ptr[c + 1]; j += kWave) {
+    const double t = s.csc_w[j] * s.x[s.csc_v[j]];
+    u = fat ? fmax(u, t) : u + t;
+  }
+  return fat ? wave_max(u) : wave_sum(u);
+}
+
 // Saturated set of the solved system: sat(c) = NOT double_positive(bound - U_c,
-// bound * prec) with U_c = Constraint::get_usage() (maxmin.cpp:948-961: sum, or max for FATPIPE, of
-// w * x over the enabled elements of weight > 0 — exactly the flattened CSC of c).  One wave per
-// constraint.  FairBottleneck: sat(c) = c was erased (fair_bottleneck.cpp:129-140, ratio = +inf).
+// bound * prec) with U_c = cnst_usage_wave.  One wave per constraint.  FairBottleneck: sat(c) = c was erased
+// (fair_bottleneck.cpp:129-140, ratio = +inf).
 __global__ void __launch_bounds__(kBlock) mm_saturated(Dev s, double prec, int fair, uint8_t* out) {
   const int lane = threadIdx.x & (kWave - 1);
   for (int64_t c = (int64_t(blockIdx.x) * kBlock + threadIdx.x) / kWave; c < s.nC;
@@ -77,18 +92,34 @@ __global__ void __launch_bounds__(kBlock) mm_saturated(Dev s, double prec, int f
         out[c] = s.ratio[c] != 0.0;
       continue;
     }
-    const bool fat = s.cflags[c] & 1;
-    double u = 0.0;
-    for (uint32_t j = s.cnst_ptr[c] + lane; j < s.cnst_ptr[c + 1]; j += kWave) {
-      const double t = s.csc_w[j] * s.x[s.csc_v[j]];
-      u = fat ? fmax(u, t) : u + t;
-    }
-    u = fat ? wave_max(u) : wave_sum(u);
+    const double u = cnst_usage_wave(s, c, lane);
     if (lane == 0) {
       const double b = s.cbound[c];
       out[c] = !((b - u) > b * prec);
     }
   }
+}
+
+// Usage of every constraint of the solved system, dense order: out[c] = U_c (cnst_usage_wave), 0 for a constraint
+// without an element.  One wave per constraint; either solver kind.
+__global__ void __launch_bounds__(kBlock) mm_usage(Dev s, double* out) {
+  const int lane = threadIdx.x & (kWave - 1);
+  for (int64_t c = (int64_t(blockIdx.x) * kBlock + threadIdx.x) / kWave; c < s.nC;
+       c += int64_t(gridDim.x) * (kBlock / kWave)) {
+    const double u = cnst_usage_wave(s, c, lane);
+    if (lane == 0)
+      out[c] = u;
+  }
+}
+
+// Constraints of the solved system in the caller's id space (resident flatten): listed constraint i with a member
+// element (lany) has the dense index dcl[i] (exclusive scan of lany) and the host slot list[i].
+__global__ void __launch_bounds__(kBlock) rs_touched_cnsts(int64_t nl, const int32_t* __restrict__ list,
+                                                           const int64_t* __restrict__ lany,
+                                                           const int64_t* __restrict__ dcl, int32_t* out) {
+  for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < nl; i += int64_t(gridDim.x) * kBlock)
+    if (lany[i])
+      out[dcl[i]] = list[i];
 }
 
 // Variables of the solved system in the caller's id space: dense index d -> host slot (resident

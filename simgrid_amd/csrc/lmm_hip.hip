@@ -843,6 +843,44 @@ int lmmhip_get_saturated(lmmhip_ctx* c, uint8_t* sat) {
   return 0;
 }
 
+// mm_usage over the solved system into the context's usage scratch, on the context's stream (not synchronised)
+static int launch_usage(lmmhip_ctx* c, double** out) {
+  if (!c || !c->uploaded || !c->solved)
+    return fail(LMMHIP_E_STATE, "no solved system");
+  HIPCHK(hipSetDevice(c->device));
+  if (int rc = scratch(c, c->usage_out, c->d.nC, out))
+    return rc;
+  if (c->d.nC) {
+    hipLaunchKernelGGL(mm_usage, dim3(grid_for(c->d.nC, kBlock / kWave)), dim3(kBlock), 0, c->stream, c->d, *out);
+    HIPCHK(hipGetLastError());
+  }
+  return 0;
+}
+
+int lmmhip_get_usage(lmmhip_ctx* c, double* usage) {
+  if (!c || !c->uploaded || !c->solved)
+    return fail(LMMHIP_E_STATE, "no solved system");
+  if (!usage && c->d.nC)
+    return fail(LMMHIP_E_ARG, "null output");
+  double* o = nullptr;
+  if (int rc = launch_usage(c, &o))
+    return rc;
+  if (c->d.nC)
+    HIPCHK(hipMemcpyAsync(usage, o, sizeof(double) * size_t(c->d.nC), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int lmmhip_usage_device_ptr(lmmhip_ctx* c, const double** dptr) {
+  if (!dptr)
+    return fail(LMMHIP_E_ARG, "null output");
+  double* o = nullptr;
+  if (int rc = launch_usage(c, &o))
+    return rc;
+  *dptr = o;
+  return 0;
+}
+
 int lmmhip_components(lmmhip_ctx* c, int32_t* var_label, int32_t* cnst_label, int64_t* ncomp) {
   if (!c || !c->uploaded)
     return fail(LMMHIP_E_STATE, "no system uploaded");
@@ -917,6 +955,39 @@ int lmmhip_get_touched_vars(lmmhip_ctx* c, int32_t* ids, int64_t cap, int64_t* n
   }
   if (nv)
     HIPCHK(hipMemcpyAsync(ids, o, size_t(nv) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int lmmhip_get_touched_cnsts(lmmhip_ctx* c, int32_t* ids, int64_t cap, int64_t* n) {
+  if (!c || !c->uploaded || !n)
+    return fail(LMMHIP_E_STATE, "no system uploaded / null count");
+  const int64_t nc = c->d.nC;
+  *n = nc;
+  if (!ids)
+    return 0;  // size query
+  if (cap < nc)
+    return fail(LMMHIP_E_ARG, "touched constraints: output capacity below the system's constraint count");
+  HIPCHK(hipSetDevice(c->device));
+  if (!c->res_flat) {  // lmmhip_upload: the caller's ids are the dense indices
+    for (int64_t k = 0; k < nc; k++)
+      ids[k] = int32_t(k);
+    return 0;
+  }
+  // resident flatten: the list, its member mask and the mask's scan are kept with the flattened structure (the
+  // refresh path reads them too)
+  int32_t* o = nullptr;
+  if (int rc = scratch(c, c->tc_out, nc, &o))
+    return rc;
+  const int64_t nl = int64_t(c->res_last_list.size());
+  if (nl) {
+    hipLaunchKernelGGL(rs_touched_cnsts, dim3(grid_for(nl, kBlock)), dim3(kBlock), 0, c->stream, nl,
+                       static_cast<const int32_t*>(c->rs_list.p), static_cast<const int64_t*>(c->rs_lany.p),
+                       static_cast<const int64_t*>(c->rs_dcl.p), o);
+    HIPCHK(hipGetLastError());
+  }
+  if (nc)
+    HIPCHK(hipMemcpyAsync(ids, o, size_t(nc) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }

@@ -28,8 +28,8 @@
 
 namespace lmmdev {
 
-// (mm_elem_usage, mm_dup_check, mm_ctl_out, mm_saturated and rs_touched, which other parts of the driver launch too,
-// are in lmm_common_kernels.hpp.)
+// (mm_elem_usage, mm_dup_check, mm_ctl_out, mm_saturated, mm_usage, rs_touched and rs_touched_cnsts, which other parts
+// of the driver launch too, are in lmm_common_kernels.hpp.)
 
 // Init, one wave per constraint: maxmin.cpp:520-555.  remaining = bound; skipped when
 // bound <= bound*prec; usage = sum (SHARED) or max (FATPIPE) of w/p over the active elements.

@@ -734,6 +734,7 @@ void System::flatten_maxmin(Flat& f, const std::vector<Id>& list) {
       any = elems_[e].weight > 0 && vmark[elems_[e].var];
     if (any) {
       dense_c[c] = coff + nc++;
+      f.dense_cnsts.push_back(c);
       f.cbound.push_back(k.bound);
       f.cflags.push_back(k.policy == SharingPolicy::FATPIPE ? 1 : 0);
     }
@@ -787,6 +788,7 @@ void System::flatten_fair(Flat& f) {
     }
     if (any) {
       dense_c[c] = coff + nc++;
+      f.dense_cnsts.push_back(c);
       f.cbound.push_back(k.bound);
       f.cflags.push_back(uint8_t((k.policy == SharingPolicy::FATPIPE ? 1 : 0) | (zero_w ? 2 : 0)));
     }
@@ -852,6 +854,7 @@ void System::finish_solve() {
 // solve
 // ------------------------------------------------------------------------------------------
 void System::prepare() {
+  dev_solved_ = false;
   if (resident_) {
     prepare_resident();
     return;
@@ -887,6 +890,30 @@ void System::device_solve() {
   lmmhip_get_stats(ctx(), &st);
   stats_.rounds = st.rounds;
   stats_.device_ms = st.device_ms;
+  dev_solved_ = true;
+  dev_resident_ = res_prepared_;
+}
+
+int64_t System::device_usage(int64_t* ids, double* usage, int64_t cap) {
+  check(dev_solved_, "device_usage: no device solve of this system to read usages from");
+  std::vector<int32_t> rid;
+  int64_t n = int64_t(flat_.dense_cnsts.size());
+  if (dev_resident_ && lmmhip_get_touched_cnsts(ctx(), nullptr, 0, &n))
+    fatal(std::string("device usage failed: ") + lmmhip_last_error());
+  if (!ids && !usage)
+    return n;
+  check(ids && usage && cap >= n, "device_usage: arrays smaller than the solved system's constraint count");
+  if (dev_resident_) {
+    rid.resize(size_t(n));
+    if (lmmhip_get_touched_cnsts(ctx(), rid.data(), n, &n))
+      fatal(std::string("device usage failed: ") + lmmhip_last_error());
+    std::copy(rid.begin(), rid.end(), ids);
+  } else {
+    std::copy(flat_.dense_cnsts.begin(), flat_.dense_cnsts.end(), ids);
+  }
+  if (lmmhip_get_usage(ctx(), usage))
+    fatal(std::string("device usage failed: ") + lmmhip_last_error());
+  return n;
 }
 
 void System::fetch() {
@@ -933,6 +960,7 @@ void System::set_resident(bool on) {
   resident_ = on;
   res_full_ = true;
   res_prepared_ = false;
+  dev_solved_ = false;
   res_de_.clear();
   res_dv_.clear();
   res_dc_.clear();

@@ -112,6 +112,13 @@ public:
   void device_solve();
   void fetch();
 
+  // Usage of the constraints of the last device solve, computed on the device from the values in HBM
+  // (lmmhip_get_usage): the flattened constraints in dense order, ids[d] with usage[d].  Works after device_solve()
+  // with no fetch(), resident or not.  Returns the count; null arrays = size query; throws before any device solve.
+  // Nothing is kept per constraint slot between solves (a constraint can leave every list without being solved
+  // again, so a kept table would go stale).
+  int64_t device_usage(int64_t* ids, double* usage, int64_t cap);
+
   // read API (maxmin.hpp:296-331, :188-247)
   double get_value(Id v) const { return values_[v]; }
   double get_bound(Id v) const { return vars_[v].bound; }
@@ -143,6 +150,7 @@ public:
   const SolveStats& last_stats() const { return stats_; }
   // solve_batch: the union's solve ran on this system's context (the first of the batch)
   void set_batch_stats(int64_t rounds, double device_ms, int64_t n_var, int64_t n_cnst, int64_t nnz) {
+    dev_solved_ = false;  // the context holds the union, not this system's own flatten
     stats_.rounds = rounds;
     stats_.device_ms = device_ms;
     stats_.n_var = n_var;
@@ -164,6 +172,7 @@ public:
     std::vector<double> weight, penalty, vbound, cbound;
     std::vector<uint8_t> cflags;
     std::vector<Id> dense_vars;  // dense index -> variable id
+    std::vector<Id> dense_cnsts;  // dense index -> constraint id
     // FairBottleneck: CSR element index of every CSC position, constraint-major, each constraint's
     // elements in the order of its enabled_element_set_ (the order bottleneck_solve subtracts them in,
     // fair_bottleneck.cpp:111-116); empty = the device's default order (lmmhip_upload2)
@@ -262,6 +271,8 @@ private:
   lmmhip_ctx* ctx_ = nullptr;
   Flat flat_;
   bool flat_valid_ = false;
+  bool dev_solved_ = false;    // the context holds a solve of the last prepare()'s system (device_usage)
+  bool dev_resident_ = false;  // ... which was flattened on the device (its constraint map: lmmhip_get_touched_cnsts)
   std::vector<double> xbuf_;
   SolveStats stats_;
 };

@@ -110,6 +110,8 @@ SIGNATURES = {
     "lmm_resident_drain": (I, [P, PI64, PI64, ct.POINTER(ct.c_int32), PD, ct.POINTER(ct.c_uint8), ct.POINTER(ct.c_int32), PI64, ct.POINTER(ct.c_int32), PD, PD, ct.POINTER(ct.c_int32), PD, ct.POINTER(ct.c_uint8)]),
     "lmm_flat_export": (I, [P, PI64, PI64, ct.POINTER(ct.c_int32), PD, PD, PD, PD, ct.POINTER(ct.c_uint8), PI64]),
     "lmm_flat_export_order": (I, [P, I64, PI64]),
+    "lmm_flat_export_cnsts": (I, [P, PI64, I64]),
+    "lmm_device_usage": (I64, [P, PI64, PD, I64]),
     "lmm_solve_batch": (I, [ct.POINTER(P), I]),
     "lmm_system_device_ctx": (P, [P]),
     "lmm_check_certificate": (I, [P, D, PD, PI64, PI64]),
@@ -149,6 +151,9 @@ SIGNATURES = {
     "lmmhip_values_device_ptr": (I, [P, ct.POINTER(P)]),
     "lmmhip_get_saturated": (I, [P, ct.POINTER(ct.c_uint8)]),
     "lmmhip_get_touched_vars": (I, [P, ct.POINTER(ct.c_int32), I64, PI64]),
+    "lmmhip_get_usage": (I, [P, PD]),
+    "lmmhip_usage_device_ptr": (I, [P, ct.POINTER(P)]),
+    "lmmhip_get_touched_cnsts": (I, [P, ct.POINTER(ct.c_int32), I64, PI64]),
     "lmmhip_get_stats": (I, [P, P]),
     "lmmhip_set_profiling": (I, [P, I]),
     "lmmhip_launch_profile": (I, [P, PI, PI, ct.POINTER(ct.c_float), I]),
@@ -561,6 +566,35 @@ class System:
         out = np.empty(self.last_stats()["n_cnst"], np.uint8)
         _check_hip(lib().lmmhip_get_saturated(self.device_ctx(), out.ctypes.data_as(ct.POINTER(ct.c_uint8))))
         return out.astype(bool)
+
+    def device_usage_dense(self):
+        """Usage of every constraint of the last solve, dense constraint order, computed on the device from the
+        values it holds (lmmhip_get_usage): the number device_saturated() is decided from."""
+        out = np.empty(self.last_stats()["n_cnst"], np.float64)
+        _check_hip(lib().lmmhip_get_usage(self.device_ctx(), out.ctypes.data_as(PD)))
+        return out
+
+    def device_usage(self):
+        """(constraint ids, usages) of the constraints of the last device solve (lmm_device_usage): int64 and
+        float64 arrays in the device's dense order.  Needs no fetch(): usable right after device_solve().  A listed
+        constraint that is not returned has usage 0; one outside the solve list (selective mode) keeps what
+        Constraint.get_usage() gives."""
+        n = lib().lmm_device_usage(self.h, None, None, 0)
+        if n < 0:
+            raise LmmError(lib().lmm_last_error().decode())
+        ids, u = np.empty(n, np.int64), np.empty(n, np.float64)
+        if lib().lmm_device_usage(self.h, ids.ctypes.data_as(PI64), u.ctypes.data_as(PD), n) != n:
+            raise LmmError(lib().lmm_last_error().decode())
+        return ids, u
+
+    def flat_cnst_ids(self):
+        """Constraint id of every dense constraint of the system multi.export_flat(self) describes
+        (lmm_flat_export_cnsts; host only, the same flatten)."""
+        cnt = (I64 * 3)()
+        _check(lib().lmm_flat_export(self.h, cnt, None, None, None, None, None, None, None, None))
+        ids = np.empty(cnt[1], np.int64)
+        _check(lib().lmm_flat_export_cnsts(self.h, ids.ctypes.data_as(PI64), len(ids)))
+        return ids
 
     def device_touched_vars(self):
         """Variables of the solved system in the context's id space (lmmhip_get_touched_vars)."""

@@ -314,6 +314,13 @@ class DeviceBatch:
         self._check(self.L.lmmhip_get_saturated(self.ctx, out.ctypes.data_as(ct.POINTER(ct.c_uint8))))
         return out.astype(bool)
 
+    def usage(self):
+        """The device's usage of every constraint after the last solve (lmmhip_get_usage: the number saturated() is
+        decided from for max-min), one double per dense constraint of the concatenated systems."""
+        out = np.empty(self.n_cnst, np.float64)
+        self._check(self.L.lmmhip_get_usage(self.ctx, out.ctypes.data_as(ct.POINTER(ct.c_double))))
+        return out
+
     def flat(self):
         """The concatenated flattened system as a Flat (dense ids; var_ids / csc_order unset)."""
         vp, ci, w, pen, vb, cb, cf = self.arrays
