@@ -320,6 +320,7 @@ int lmmhip_fb_work(lmmhip_ctx* ctx, int64_t* out3);
  *   penalty[i]          the variable's current penalty (finish test: remains <= 0 && penalty > 0)
  *   sharing_penalty[i]  CM02: the penalty restored when the latency is paid (network_cm02.cpp:145)
  *   flags[i]            bit0 = the variable has no constraint, bit1 = suspended
+ *   (events[i] starts at 0: no action has an event before the first update)
  * lmmhip_next_event_full: Model::next_occuring_event_full (Model.cpp:103-129), with_latency adds the
  *   network / ptask latency term (network_interface.cpp:57-70, ptask_L07.cpp:69-82); -1 = no event.
  * lmmhip_update_actions_full: update_actions_state_full of model LMMHIP_MODEL_CPU (cpu_interface.cpp:37-51),
@@ -371,6 +372,71 @@ int lmmhip_actions_lazy_due(lmmhip_ctx* ctx, int model, double now, double surf_
                             uint8_t* events, int64_t cap, int64_t* n_due);
 int lmmhip_actions_lazy_download(lmmhip_ctx* ctx, double* last_update, double* last_value, double* date,
                                  uint8_t* heap_type);
+
+/* ---- Resident action table: one table per model for the context's lifetime ----
+ * lmmhip_actions_upload's var_index holds the dense indices of ONE flatten; every lmmhip_upload and every
+ * lmmhip_res_flatten renumbers them.  A BOUND table names each action's variable in the caller's id space instead
+ * — the id space of lmmhip_get_touched_vars: the host variable slot after lmmhip_res_flatten / _flatten_fair, the
+ * dense index after lmmhip_upload, -1 = no variable — and the library follows the renumbering itself: the context
+ * counts its uploads and flattens (the refresh path included), and lmmhip_next_event_full,
+ * lmmhip_update_actions_full, lmmhip_actions_lazy_update and the calls of this block that use the dense indices
+ * (bind, patch, lazy_update_solved, var_index) first queue one kernel (act_rebind) on the context's stream when
+ * that count moved since the table's dense indices were written:
+ *   index = id < 0 ? -1 : resident flatten ? (the flatten covered the slot and put its variable in the system ?
+ *           its dense index : -1) : (id < n_var ? id : -1);   -1 for every action while no system is uploaded.
+ * An id past what the device has seen so far is "not solved", not an error: a table may be bound before the
+ * variable reaches the mirror.  An unbound table behaves as before: var_index as uploaded, never rewritten.
+ *
+ * lmmhip_actions_bind (after lmmhip_actions_upload; n = the table's size): binds the table, var_slot[i] as above.
+ *   The var_index given to lmmhip_actions_upload is then overwritten (pass -1).
+ * lmmhip_actions_patch: rewrites the fields named by the bit mask `fields` (LMMHIP_ACT_F_*) of the k actions
+ *   idx[0..k) from the arrays' entries 0..k (one staged copy, one scatter kernel); an array whose bit is clear may
+ *   be NULL and that field keeps its value.  A patched var_slot is rebound at once.  An action whose heap type
+ *   ends up LMMHIP_HEAP_UNSET gets the date +inf (as lmmhip_actions_lazy_upload).  The events array is not
+ *   touched.  Checked on the host before any device work, LMMHIP_E_ARG: an index outside the table, an index
+ *   listed twice, var_slot < -1, an unknown heap type, a lazy field (last_update .. heap_type) before
+ *   lmmhip_actions_lazy_upload, an unknown bit, a NULL array whose bit is set; LMMHIP_E_STATE: no table uploaded,
+ *   or LMMHIP_ACT_F_VAR_SLOT on an unbound table.  A failed patch changes nothing.
+ * Vacant entries: the record {var_slot -1, remains 0, max_duration -1, latency 0, penalty 0, flags 0,
+ *   heap type UNSET} yields no event, no date and no term of either next-event reduction in any pass.  Upload a
+ *   table of such records to reserve capacity, patch one to start an action, patch it back to retire the action.
+ *   When the host System reuses a variable slot, the action that was bound to it must have been retired or
+ *   re-patched first: the table cannot tell the new variable from the old one.
+ * lmmhip_actions_lazy_update_solved (bound table, after lmmhip_actions_lazy_upload and a solve): the loop of
+ *   lmmhip_actions_lazy_update over the modified set taken on the device — every action whose variable is in the
+ *   system of the last flatten (dense index >= 0: the Lazy modified_set_, maxmin.cpp:536-538), plus the actions
+ *   extra[0..n_extra) the model pushed by hand (cpu_cas01.cpp:196); an action in both, or listed twice, is
+ *   processed once.  One pass over the table: events[i] is written for EVERY action (0 outside the set).
+ *   *n_modified = size of the set, *n_finished as lmmhip_actions_lazy_update.  LMMHIP_E_STATE on an unbound
+ *   table, and for DIE_IMPOSSIBLE as lmmhip_actions_lazy_update.
+ * lmmhip_actions_events: the actions whose events entry is non-zero — after lmmhip_update_actions_full and
+ *   lmmhip_actions_lazy_update_solved exactly the events of that pass; lmmhip_actions_lazy_update and
+ *   lmmhip_actions_lazy_due write only the entries of the actions they process — compacted on the device, in
+ *   ascending action index, with their codes.  *n = count; ids == events == NULL = size query; cap >= *n.
+ * lmmhip_actions_var_index: inspection, the dense indices in force (after a pending rebind), n int32. */
+#define LMMHIP_ACT_F_VAR_SLOT 1
+#define LMMHIP_ACT_F_REMAINS 2
+#define LMMHIP_ACT_F_MAX_DURATION 4
+#define LMMHIP_ACT_F_LATENCY 8
+#define LMMHIP_ACT_F_PENALTY 16
+#define LMMHIP_ACT_F_SHARING_PENALTY 32
+#define LMMHIP_ACT_F_FLAGS 64
+#define LMMHIP_ACT_F_LAST_UPDATE 128
+#define LMMHIP_ACT_F_LAST_VALUE 256
+#define LMMHIP_ACT_F_START_TIME 512
+#define LMMHIP_ACT_F_DATE 1024
+#define LMMHIP_ACT_F_HEAP_TYPE 2048
+int lmmhip_actions_bind(lmmhip_ctx* ctx, int64_t n, const int32_t* var_slot);
+int lmmhip_actions_patch(lmmhip_ctx* ctx, int64_t k, const int32_t* idx, int fields, const int32_t* var_slot,
+                         const double* remains, const double* max_duration, const double* latency,
+                         const double* penalty, const double* sharing_penalty, const uint8_t* flags,
+                         const double* last_update, const double* last_value, const double* start_time,
+                         const double* date, const uint8_t* heap_type);
+int lmmhip_actions_lazy_update_solved(lmmhip_ctx* ctx, int model, double now, double maxmin_precision,
+                                      double surf_precision, int64_t n_extra, const int32_t* extra,
+                                      int64_t* n_modified, int64_t* n_finished);
+int lmmhip_actions_events(lmmhip_ctx* ctx, int32_t* ids, uint8_t* events, int64_t cap, int64_t* n);
+int lmmhip_actions_var_index(lmmhip_ctx* ctx, int32_t* out);
 
 /* Number of visible HIP devices (0 when none; never initialises a context). */
 int lmmhip_device_count(void);

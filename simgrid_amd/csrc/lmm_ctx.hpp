@@ -278,6 +278,12 @@ struct lmmhip_ctx {
   Arena fbo_allocs;
   ActDev act{};                        // model-side action state (lmm_step_kernels.hpp)
   Arena act_allocs;
+  // bound action table (lmmhip_actions_bind): the caller's variable id of every action (in act_allocs); sys_gen
+  // counts the uploads and flattens (alloc_flat, finish_flat, the resident refresh path), act_gen is the sys_gen
+  // act.vidx was last rebound at (act_rebind, queued by the step entry points when the two differ)
+  int32_t* act_slot = nullptr;
+  uint64_t sys_gen = 1, act_gen = 0;
+  Scr act_stage, act_mask, act_evout;  // lmmhip_actions_patch staging, the `extra` byte mask, lmmhip_actions_events
   int32_t* xnb_own = nullptr;  // the context's own exchange buffers (unsharded solves; in `allocs`)
   double* xmin_own = nullptr;
   int64_t fbd_cap = 0;  // elements of d.fbd (allocated by the first one-context FairBottleneck solve)

@@ -255,13 +255,14 @@ struct FbOwner {
 // Model-side action state (lmm_step_kernels.hpp).
 struct ActDev {
   int64_t n;
-  const int32_t* vidx;     // dense variable index of each action's variable, -1 = not solved (value 0)
+  int32_t* vidx;           // dense variable index of each action's variable, -1 = not solved (value 0);
+                           // a bound table's is rewritten by act_rebind after every upload / flatten
   double* remains;
   double* max_duration;
   double* latency;
   double* penalty;         // the variable's current penalty (finish test)
-  const double* share_pen; // CM02: sharing penalty restored once the latency is paid
-  const uint8_t* flags;    // ACT_NO_CNST, ACT_SUSPENDED
+  double* share_pen;       // CM02: sharing penalty restored once the latency is paid
+  uint8_t* flags;          // ACT_NO_CNST, ACT_SUSPENDED
   uint8_t* events;         // EV_* of the last update
   unsigned long long* umin;  // next-event reduction (bit pattern of a non-negative double)
   int32_t* nev;            // number of actions with an event in the last update
@@ -269,12 +270,23 @@ struct ActDev {
   // action's ActionHeap entry (date + type) — the heap itself is a min-reduction over `date`.
   double* last_update;
   double* last_value;
-  const double* start_time;
+  double* start_time;
   double* date;            // heap date (+inf when not in the heap)
   uint8_t* htype;          // HEAP_*
   int32_t* due;            // compacted due actions (lmmhip_actions_lazy_due)
   int32_t* ndue;
   int32_t* err;            // DIE_IMPOSSIBLE of next_occuring_event_lazy (Model.cpp:95-96)
+};
+
+// How a bound action table (lmmhip_actions_bind) finds its variables in the system the context holds now: the
+// caller's variable id -> dense index (act_dense, lmm_step_kernels.hpp).
+enum : int { BIND_NONE = 0, BIND_DENSE = 1, BIND_RESIDENT = 2 };
+struct ActBind {
+  int mode;           // BIND_NONE: no system uploaded; BIND_DENSE: lmmhip_upload, the ids are the dense indices;
+                      // BIND_RESIDENT: a resident flatten, the ids are host variable slots
+  int64_t nv;         // BIND_DENSE: dense variables; BIND_RESIDENT: variable slots the flatten covered
+  const int64_t* vm;  // BIND_RESIDENT: [nv] 1 = the flatten put the slot's variable in the system (rs_mark) ...
+  const int64_t* dv;  // ... at this dense index (the exclusive scan of vm)
 };
 
 // sizes the host code of more than one translation unit needs

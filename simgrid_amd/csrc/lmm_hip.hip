@@ -208,6 +208,7 @@ static int alloc_flat_exact(lmmhip_ctx* c, int64_t nV, int64_t nC, int64_t nnz, 
 // simulation re-solves systems of similar size every step: no hipMalloc / hipFree on that path);
 // otherwise reallocated with 25 % headroom over the previous capacity.
 int alloc_flat(lmmhip_ctx* c, int64_t nV, int64_t nC, int64_t nnz, int64_t nch, FlatBufs* o) {
+  c->sys_gen++;  // the dense numbering is about to change (bound action tables rebind)
   const bool have = !c->allocs.v.empty();
   const bool fits = have && nV <= c->fcap[0] && nC <= c->fcap[1] && nnz <= c->fcap[2] && nch <= c->fcap[3];
   if (!fits) {
@@ -257,6 +258,7 @@ int finish_flat(lmmhip_ctx* c, int64_t nV, int64_t nC, int64_t nnz, bool elem_do
     HIPCHK(hipStreamSynchronize(c->stream));
   }
   c->uploaded = true;
+  c->sys_gen++;
   c->solved = false;
   c->bt_n = 0;  // a new system: no batch declared
   c->stats = lmmhip_stats{};

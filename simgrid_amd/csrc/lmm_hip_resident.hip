@@ -199,6 +199,7 @@ static int res_flatten(lmmhip_ctx* c, bool fair, int64_t n_list, const int32_t* 
       HIPCHK(hipMemsetAsync(c->res_dirty.p + 3, 0, sizeof(int32_t), c->stream));
       HIPCHK(hipStreamSynchronize(c->stream));
       c->res_refreshes++;
+      c->sys_gen++;  // (the dense maps stand; every flatten counts, so that a rebind never depends on which path ran)
       c->res_cross_refreshes += nx > 0;
       if (counts3) {
         counts3[0] = d.nV;

@@ -10,6 +10,10 @@
 //                   and max-duration updates with double_update (surf_interface.hpp:34-42) and the
 //                   finish test.  Every action is independent: element-wise IEEE arithmetic in the
 //                   reference's order (built with -ffp-contract=off), so results are bit-identical.
+//   act_rebind / act_patch / act_lazy_update_solved / act_events
+//                   the resident table (lmmhip_actions_bind): dense indices rewritten from the bound variable
+//                   ids after a flatten, single actions rewritten, the Lazy modified set taken from those
+//                   indices, the actions with an event compacted.  Streaming passes like the ones above.
 #pragma once
 #include "lmm_dev.hpp"
 
@@ -118,58 +122,175 @@ __device__ __forceinline__ unsigned long long dorder(double d) {
 // the entry is (re)written even for an action that update_remains_lazy just finished, as in the
 // reference).  The second update_remains_lazy hidden in Action::get_remains() (Action.cpp:184-192) runs
 // at delta = 0 and changes nothing, so it is not repeated.
+// Returns false for an action the loop skips (nothing of it is written, its event included), else true with *ev the
+// action's event.
+__device__ __forceinline__ bool lazy_update_one(const ActDev& a, const double* x, int model, double now, double rprec,
+                                                double sprec, int64_t i, uint8_t* evp) {
+  const uint8_t fl = a.flags[i];
+  if (fl & ACT_NOT_STARTED)
+    return false;
+  const double pen = a.penalty[i];
+  if (pen <= 0 || a.htype[i] == HEAP_LATENCY)
+    return false;
+  const int32_t k = a.vidx[i];
+  const double value = k >= 0 ? x[k] : 0.0;
+  double rem = a.remains[i], md = a.max_duration[i];
+  const double delta = now - a.last_update[i];
+  uint8_t ev = 0;
+  if (rem > 0)
+    double_update(rem, a.last_value[i] * delta, rprec);
+  if (model != MODEL_CPU) {
+    if (md != kNoMaxDuration)
+      double_update(md, delta, sprec);
+    if ((rem <= 0 && pen > 0) || (md != kNoMaxDuration && md <= 0))
+      ev = EV_FINISHED;
+  }
+  a.last_update[i] = now;
+  a.last_value[i] = value;
+  double mn = -1;
+  if (value > 0) {
+    const double ttc = rem > 0 ? rem / value : 0.0;
+    mn = now + ttc;
+  }
+  bool mdflag = false;
+  const double st = a.start_time[i];
+  if (md != kNoMaxDuration && (mn <= -1 || st + md < mn)) {
+    mn = st + md;
+    mdflag = true;
+  }
+  if (mn > -1) {
+    a.date[i] = mn;
+    a.htype[i] = mdflag ? HEAP_MAX_DURATION : HEAP_NORMAL;
+  } else {
+    atomicOr(a.err, 1);
+  }
+  a.remains[i] = rem;
+  a.max_duration[i] = md;
+  a.events[i] = ev;
+  *evp = ev;
+  return true;
+}
+
 __global__ void __launch_bounds__(kBlock) act_lazy_update(ActDev a, const double* x, int model, double now,
                                                            double rprec, double sprec, int64_t nmod,
                                                            const int32_t* __restrict__ mod) {
   int nev = 0;
   for (int64_t j = int64_t(blockIdx.x) * kBlock + threadIdx.x; j < nmod; j += int64_t(gridDim.x) * kBlock) {
-    const int32_t i = mod[j];
-    const uint8_t fl = a.flags[i];
-    if (fl & ACT_NOT_STARTED)
-      continue;
-    const double pen = a.penalty[i];
-    if (pen <= 0 || a.htype[i] == HEAP_LATENCY)
-      continue;
-    const int32_t k = a.vidx[i];
-    const double value = k >= 0 ? x[k] : 0.0;
-    double rem = a.remains[i], md = a.max_duration[i];
-    const double delta = now - a.last_update[i];
     uint8_t ev = 0;
-    if (rem > 0)
-      double_update(rem, a.last_value[i] * delta, rprec);
-    if (model != MODEL_CPU) {
-      if (md != kNoMaxDuration)
-        double_update(md, delta, sprec);
-      if ((rem <= 0 && pen > 0) || (md != kNoMaxDuration && md <= 0))
-        ev = EV_FINISHED;
-    }
-    a.last_update[i] = now;
-    a.last_value[i] = value;
-    double mn = -1;
-    if (value > 0) {
-      const double ttc = rem > 0 ? rem / value : 0.0;
-      mn = now + ttc;
-    }
-    bool mdflag = false;
-    const double st = a.start_time[i];
-    if (md != kNoMaxDuration && (mn <= -1 || st + md < mn)) {
-      mn = st + md;
-      mdflag = true;
-    }
-    if (mn > -1) {
-      a.date[i] = mn;
-      a.htype[i] = mdflag ? HEAP_MAX_DURATION : HEAP_NORMAL;
-    } else {
-      atomicOr(a.err, 1);
-    }
-    a.remains[i] = rem;
-    a.max_duration[i] = md;
-    a.events[i] = ev;
-    nev += ev != 0;
+    if (lazy_update_one(a, x, model, now, rprec, sprec, mod[j], &ev))
+      nev += ev != 0;
   }
   nev = grp_isum<kWave>(nev);
   if ((threadIdx.x & (kWave - 1)) == 0 && nev)
     atomicAdd(a.nev, nev);
+}
+
+// ---- bound table (lmmhip_actions_bind): the actions name their variables in the caller's id space ----
+// Dense index of the caller's variable id `slot` in the system the context holds (-1: not solved).  A slot past
+// what the last flatten covered is a variable the device has not seen yet: not solved, no error.
+__device__ __forceinline__ int32_t act_dense(const ActBind& b, int32_t slot) {
+  if (slot < 0 || b.mode == BIND_NONE || slot >= b.nv)
+    return -1;
+  if (b.mode == BIND_DENSE)
+    return slot;
+  return b.vm[slot] ? int32_t(b.dv[slot]) : -1;
+}
+
+// vidx of every action from its bound id, after an upload or a flatten renumbered the dense variables.
+__global__ void __launch_bounds__(kBlock) act_rebind(int64_t n, const int32_t* __restrict__ slot, ActBind b,
+                                                      int32_t* __restrict__ vidx) {
+  for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += int64_t(gridDim.x) * kBlock)
+    vidx[i] = act_dense(b, slot[i]);
+}
+
+// lmmhip_actions_patch: k actions (idx ascending: the host sorts the patch, so the scattered stores of a wave walk
+// the arrays in address order and a dense patch coalesces), the fields named by `fields` (LMMHIP_ACT_F_* bit f =
+// PatchSrc field f) from the staged arrays, each a coalesced SoA read.  A patched variable id is rebound here;
+// an entry whose heap type ends up UNSET gets the date +inf (as lmmhip_actions_lazy_upload).
+enum : int {
+  PF_VAR_SLOT = 1, PF_REMAINS = 2, PF_MAX_DURATION = 4, PF_LATENCY = 8, PF_PENALTY = 16, PF_SHARE_PEN = 32,
+  PF_FLAGS = 64, PF_LAST_UPDATE = 128, PF_LAST_VALUE = 256, PF_START_TIME = 512, PF_DATE = 1024,
+  PF_HEAP_TYPE = 2048, PF_ALL = 4095, PF_LAZY = PF_LAST_UPDATE | PF_LAST_VALUE | PF_START_TIME | PF_DATE | PF_HEAP_TYPE
+};
+struct PatchSrc {
+  const int32_t *idx, *slot;
+  const double *remains, *max_duration, *latency, *penalty, *share_pen, *last_update, *last_value, *start_time, *date;
+  const uint8_t *flags, *htype;
+};
+__global__ void __launch_bounds__(kBlock) act_patch(ActDev a, int32_t* bslot, ActBind b, int64_t k, int fields,
+                                                     PatchSrc s) {
+  for (int64_t j = int64_t(blockIdx.x) * kBlock + threadIdx.x; j < k; j += int64_t(gridDim.x) * kBlock) {
+    const int64_t i = s.idx[j];
+    if (fields & PF_VAR_SLOT) {
+      const int32_t sl = s.slot[j];
+      bslot[i] = sl;
+      a.vidx[i] = act_dense(b, sl);
+    }
+    if (fields & PF_REMAINS)
+      a.remains[i] = s.remains[j];
+    if (fields & PF_MAX_DURATION)
+      a.max_duration[i] = s.max_duration[j];
+    if (fields & PF_LATENCY)
+      a.latency[i] = s.latency[j];
+    if (fields & PF_PENALTY)
+      a.penalty[i] = s.penalty[j];
+    if (fields & PF_SHARE_PEN)
+      a.share_pen[i] = s.share_pen[j];
+    if (fields & PF_FLAGS)
+      a.flags[i] = s.flags[j];
+    if (fields & PF_LAST_UPDATE)
+      a.last_update[i] = s.last_update[j];
+    if (fields & PF_LAST_VALUE)
+      a.last_value[i] = s.last_value[j];
+    if (fields & PF_START_TIME)
+      a.start_time[i] = s.start_time[j];
+    if (fields & (PF_DATE | PF_HEAP_TYPE)) {
+      const uint8_t h = (fields & PF_HEAP_TYPE) ? s.htype[j] : a.htype[i];
+      if (fields & PF_HEAP_TYPE)
+        a.htype[i] = h;
+      if (h == HEAP_UNSET)
+        a.date[i] = dinf();
+      else if (fields & PF_DATE)
+        a.date[i] = s.date[j];
+    }
+  }
+}
+
+// lmmhip_actions_lazy_update_solved: the loop of act_lazy_update over the modified set taken here — every action
+// whose (rebound) variable is in the solved system, plus the caller's `extra` actions (a byte mask, null = none) —
+// in one pass over the table.  Every action's event is written: 0 for the ones outside the set or skipped.
+__global__ void __launch_bounds__(kBlock) act_lazy_update_solved(ActDev a, const double* x, int model, double now,
+                                                                  double rprec, double sprec,
+                                                                  const uint8_t* __restrict__ extra, int* nmod_out) {
+  int nev = 0, nmod = 0;
+  for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < a.n; i += int64_t(gridDim.x) * kBlock) {
+    uint8_t ev = 0;
+    if (a.vidx[i] >= 0 || (extra && extra[i])) {
+      nmod++;
+      if (!lazy_update_one(a, x, model, now, rprec, sprec, i, &ev))
+        a.events[i] = 0;
+    } else {
+      a.events[i] = 0;
+    }
+    nev += ev != 0;
+  }
+  nev = grp_isum<kWave>(nev);
+  nmod = grp_isum<kWave>(nmod);
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    if (nev)
+      atomicAdd(a.nev, nev);
+    if (nmod)
+      atomicAdd(nmod_out, nmod);
+  }
+}
+
+// lmmhip_actions_events: the actions with an event, compacted as (index << 8 | event) words (the host sorts them).
+__global__ void __launch_bounds__(kBlock) act_events(ActDev a, unsigned long long* out, int32_t* nout) {
+  for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < a.n; i += int64_t(gridDim.x) * kBlock) {
+    const uint8_t ev = a.events[i];
+    if (ev)
+      out[atomicAdd(nout, 1)] = (unsigned long long)i << 8 | ev;
+  }
 }
 
 // ActionHeap::top_date(): min over the heap entries (dorder-encoded).

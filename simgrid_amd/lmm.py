@@ -184,6 +184,12 @@ SIGNATURES = {
     "lmmhip_next_event_lazy": (I, [P, D, PD]),
     "lmmhip_actions_lazy_due": (I, [P, I, D, D, ct.POINTER(ct.c_int32), ct.POINTER(ct.c_uint8), I64, PI64]),
     "lmmhip_actions_lazy_download": (I, [P, PD, PD, PD, ct.POINTER(ct.c_uint8)]),
+    "lmmhip_actions_bind": (I, [P, I64, ct.POINTER(ct.c_int32)]),
+    "lmmhip_actions_patch": (I, [P, I64, ct.POINTER(ct.c_int32), I, ct.POINTER(ct.c_int32), PD, PD, PD, PD, PD,
+                                 ct.POINTER(ct.c_uint8), PD, PD, PD, PD, ct.POINTER(ct.c_uint8)]),
+    "lmmhip_actions_lazy_update_solved": (I, [P, I, D, D, D, I64, ct.POINTER(ct.c_int32), PI64, PI64]),
+    "lmmhip_actions_events": (I, [P, ct.POINTER(ct.c_int32), ct.POINTER(ct.c_uint8), I64, PI64]),
+    "lmmhip_actions_var_index": (I, [P, ct.POINTER(ct.c_int32)]),
     "lmmhip_device_count": (I, []),
     "lmmhip_last_error": (ct.c_char_p, []),
     "lmmhip_build_id": (ct.c_char_p, []),

@@ -14,6 +14,12 @@ model run as kernels (lmm_step_kernels.hpp) through the lmmhip_* step ABI:
 Only the events (finished actions, paid latencies) go back to the host, which then does what the
 reference does with them: Action::finish, update_variable_penalty (and, for L07, updateBound).  With
 several GPUs, the step date is multi.next_event_date over the ranks' `next_occuring_event`.
+
+A model keeps ONE table for its lifetime (the resident table): `DeviceActions.reserve(ctx, capacity)` uploads
+vacant entries once, `bind` names every action's variable in the caller's id space (the host variable slot of a
+resident System) so the library follows each flatten's renumbering on the device, `patch` starts, changes and
+retires single actions, `lazy_update_solved` takes the Lazy modified set on the device, and `events` returns
+only the actions that have one.
 """
 import ctypes as ct
 
@@ -27,6 +33,15 @@ ACT_NO_CNST, ACT_SUSPENDED, ACT_NOT_STARTED = 1, 2, 4
 HEAP_UNSET, HEAP_LATENCY, HEAP_MAX_DURATION, HEAP_NORMAL = 0, 1, 2, 3  # ActionHeap::Type
 NO_MAX_DURATION = -1.0
 SURF_PRECISION = 1e-5  # --cfg=surf/precision default
+
+# lmmhip_actions_patch: field name -> (LMMHIP_ACT_F_* bit, dtype), in the ABI's argument order
+PATCH_FIELDS = {"var_slot": (1, np.int32), "remains": (2, np.float64), "max_duration": (4, np.float64),
+                "latency": (8, np.float64), "penalty": (16, np.float64), "sharing_penalty": (32, np.float64),
+                "flags": (64, np.uint8), "last_update": (128, np.float64), "last_value": (256, np.float64),
+                "start_time": (512, np.float64), "date": (1024, np.float64), "heap_type": (2048, np.uint8)}
+# the vacant entry (include/lmm/lmm_hip.h): no event, no date, no term of a next-event reduction in any pass
+VACANT = dict(var_slot=-1, remains=0.0, max_duration=NO_MAX_DURATION, latency=0.0, penalty=0.0, sharing_penalty=0.0,
+              flags=0, last_update=0.0, last_value=0.0, start_time=0.0, date=float("inf"), heap_type=HEAP_UNSET)
 
 
 def dense_index(flat_var_ids, action_vars):
@@ -61,9 +76,70 @@ class DeviceActions:
                                                  _p(md, ct.c_double), _p(lat, ct.c_double), _p(pen, ct.c_double),
                                                  _p(sp, ct.c_double), _p(fl, ct.c_uint8)))
 
+    @classmethod
+    def reserve(cls, ctx, capacity, lazy=False):
+        """A bound table of `capacity` vacant entries (VACANT), with the lazy state when `lazy`: the table a model
+        keeps for its lifetime; `patch` starts and retires its actions."""
+        acts = cls(ctx, np.full(capacity, -1, np.int32), np.zeros(capacity), penalty=np.zeros(capacity),
+                   sharing_penalty=np.zeros(capacity))
+        if lazy:
+            acts.lazy_init()
+        acts.bind(np.full(capacity, -1, np.int32))
+        return acts
+
     def _check(self, rc):
         if rc != 0:
             raise lmm.LmmError(self.L.lmmhip_last_error().decode())
+
+    # ---- resident table ----
+    def bind(self, var_slots):
+        """Bind action i to the variable var_slots[i] of the caller's id space (lmmhip_actions_bind): the host
+        variable slot (Variable.h) of a resident System, the dense index after a host flatten, -1 = none."""
+        vs = np.ascontiguousarray(var_slots, dtype=np.int32)
+        self._check(self.L.lmmhip_actions_bind(self.ctx, len(vs), _p(vs, ct.c_int32)))
+
+    def patch(self, idx, **fields):
+        """Rewrite the named fields (PATCH_FIELDS; a scalar or one value per index) of the actions `idx`
+        (lmmhip_actions_patch)."""
+        ix = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+        unknown = set(fields) - set(PATCH_FIELDS)
+        if unknown:
+            raise TypeError(f"patch: unknown field(s) {sorted(unknown)}")
+        mask, args = 0, []
+        for name, (bit, dtype) in PATCH_FIELDS.items():
+            if name not in fields:
+                args.append(None)
+                continue
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(fields[name], dtype=dtype), ix.shape))
+            mask |= bit
+            args.append(_p(a, np.ctypeslib.as_ctypes_type(dtype)))
+            fields[name] = a  # keeps the array alive for the call
+        self._check(self.L.lmmhip_actions_patch(self.ctx, len(ix), _p(ix, ct.c_int32), mask, *args))
+
+    def lazy_update_solved(self, model, now, extra=(), maxmin_precision=None, surf_precision=SURF_PRECISION):
+        """`lazy_update` over the modified set taken on the device: the actions whose variable is in the solved
+        system, plus `extra`.  Returns (n_modified, n_finished)."""
+        mp = lmm.get_precision() if maxmin_precision is None else maxmin_precision
+        ex = np.ascontiguousarray(extra, dtype=np.int32).reshape(-1)
+        nm, nf = ct.c_int64(), ct.c_int64()
+        self._check(self.L.lmmhip_actions_lazy_update_solved(self.ctx, model, now, mp, surf_precision, len(ex),
+                                                             _p(ex, ct.c_int32), ct.byref(nm), ct.byref(nf)))
+        return nm.value, nf.value
+
+    def events(self):
+        """(ids, codes) of the actions with an event, ascending index (lmmhip_actions_events)."""
+        k = ct.c_int64()
+        self._check(self.L.lmmhip_actions_events(self.ctx, None, None, 0, ct.byref(k)))
+        ids, ev = np.empty(k.value, np.int32), np.empty(k.value, np.uint8)
+        self._check(self.L.lmmhip_actions_events(self.ctx, _p(ids, ct.c_int32), _p(ev, ct.c_uint8), k.value,
+                                                 ct.byref(k)))
+        return ids, ev
+
+    def var_index(self):
+        """The dense index of every action's variable in force (lmmhip_actions_var_index)."""
+        out = np.empty(self.n, np.int32)
+        self._check(self.L.lmmhip_actions_var_index(self.ctx, _p(out, ct.c_int32)))
+        return out
 
     def next_occuring_event(self, with_latency=False):
         out = ct.c_double()
