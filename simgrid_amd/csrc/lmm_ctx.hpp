@@ -10,6 +10,13 @@
 //
 // Every __global__ kernel is compiled in exactly one of them (each kernel header is included by one unit); a
 // kernel another unit needs is reached through a host function declared here.
+//
+// Three types carry the system to the device (lmm_dev.hpp).  Dev, the context's `d`: the flattened system and the
+// max-min state the round, persistent and batch engines and the getters share; their kernels take it (the round
+// engine a copy with its mode's buffers).  FrDev = Dev + FrFields: the frontier engine's kernels alone; built per
+// solve by solve_maxmin_frontier from the FrontierEngine's buffers.  FbDev = Dev + FbFields: the FairBottleneck
+// kernels alone; built per solve, and per call of the sharded protocol, from the FairEngine's `f`.  An engine cannot
+// name another's fields, and none of them is ever written into the context's Dev.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -195,11 +202,31 @@ int solve_maxmin_batch(lmmhip_ctx* c, double prec);
 int batch_rounds_to_ctl(lmmhip_ctx* c, int grid);  // mm_batch_rounds: bt_rounds[0..grid) -> CTL_ROUNDS / CTL_ERR
 int engine_of(const lmmhip_ctx* c);
 
-// one-context FairBottleneck (lmm_hip_fair.hip solve_fair): the long shared constraints (fb_long_list) and the
-// locality order of the mu gathers (fb_perm), which matches the uploaded system while perm_ok
+// FairBottleneck (lmm_hip_fair.hip): the one-context solve (solve_fair) and the sharded protocol (lmmhip_fb_shard_*).
+// `f` holds the fields of the engine's view (FbFields, lmm_dev.hpp) that live with the flat system's buffers: the
+// chunk arrays, the per-variable and per-chunk state, the context's own exchange buffers (xnb, xmin) and fbd.  A solve,
+// and each call of the sharded protocol, launches with an FbDev built from the context's Dev and `f`; what only
+// solve_fair uses (fb_long, the locality order, hprog) is null in `f` and set in that solve's view alone.
 struct FairEngine {
+  FbFields f{};
+  int64_t fbd_cap = 0;  // elements of f.fbd (allocated by the first one-context solve, with the flat system's buffers)
+  // the long shared constraints (fb_long_list) and the locality order of the mu gathers (fb_perm), which matches the
+  // uploaded system while perm_ok
   Scr longl, k0, k1, v0, v1, tmp, perm, cscvp, mu;
   bool perm_ok = false;
+  // round state of the solve in flight (solve_fair and the sharded protocol)
+  int64_t round = 0;
+  double prec = 0;
+  uint32_t longmin = 0;  // solve_fair: shared constraints with >= this many elements use fbk_acc's increments
+  int nlb = 128;         // solve_fair: fbk_update_seq workgroups for the long chains
+  // sharded solve: the caller's all-reduced listed counts (in place of f.xnb; non-null while the solve is in
+  // flight: begin sets it, an upload or a one-context solve clears it), the owned constraints
+  // (lmmhip_fb_shard_owner) and the length of the gathered mu vector their elements index
+  int32_t* shard_xnb = nullptr;
+  FbOwner owner{};
+  bool owner_ready = false;
+  int64_t owner_nmu = 0;
+  Arena owner_allocs;
 };
 int solve_fair(lmmhip_ctx* c, double prec);
 // FairBottleneck of a declared batch (lmm_hip_fair.hip, lmm_fb_batch_kernels.hpp): one workgroup per system
@@ -215,7 +242,7 @@ struct lmmhip_ctx {
   Dev d{};
   Arena allocs;            // the flat system's buffers (alloc_flat_exact)
   PinPtr<int32_t> h_ctl;   // pinned mirror of the control words (+ 2 slots: the pipelined polls, CtlPoll;
-                           // + 1: the words the device writes itself, Dev::hprog)
+                           // + 1: the words the device writes itself, FbFields::hprog)
   Event ev_poll[2];        // completion of the pipelined control-word copies
   std::vector<Event> ev_slice;  // lmmhip_res_values_sliced: completion of each slice's copy
   bool uploaded = false;
@@ -262,20 +289,10 @@ struct lmmhip_ctx {
   int bt_max_nv = 0, bt_max_nc = 0, bt_max_nnz = 0;
   size_t bt_lds = 0;  // mm_batch_lds' LDS bytes: the largest batch_lds_bytes over the systems, each by its own sizes
   int64_t bt_cap = 0;
-  // fair bottleneck round state (lmmhip_solve and the sharded lmmhip_fb_shard_* protocol)
-  int64_t fb_round = 0;
   // rounds the previous solve of this context had to queue before its termination test could fire (round engine:
   // LASTR + 1, mm_done at the end of the chunk; frontier: ROUNDS + 1, the vote after the last update): a hint for
   // where to end a chunk and wait for it (round_hint_chunk); 0 = none
   int64_t hint_rounds_mm = 0, hint_rounds_fr = 0;
-  uint32_t fb_longmin = 0;  // solve_fair: shared constraints with >= this many elements use fbk_acc's increments
-  int fb_nlb = 128;          // solve_fair: fbk_update_seq workgroups for the long chains
-  double fb_prec = 0;
-  bool fb_shard = false;
-  FbOwner fbo{};                   // sharded solve: the owned constraints (lmmhip_fb_shard_owner)
-  bool fbo_ready = false;
-  int64_t fbo_nmu = 0;  // length of the gathered mu vector the owned elements index
-  Arena fbo_allocs;
   ActDev act{};                        // model-side action state (lmm_step_kernels.hpp)
   Arena act_allocs;
   // bound action table (lmmhip_actions_bind): the caller's variable id of every action (in act_allocs); sys_gen
@@ -284,9 +301,6 @@ struct lmmhip_ctx {
   int32_t* act_slot = nullptr;
   uint64_t sys_gen = 1, act_gen = 0;
   Scr act_stage, act_mask, act_evout;  // lmmhip_actions_patch staging, the `extra` byte mask, lmmhip_actions_events
-  int32_t* xnb_own = nullptr;  // the context's own exchange buffers (unsharded solves; in `allocs`)
-  double* xmin_own = nullptr;
-  int64_t fbd_cap = 0;  // elements of d.fbd (allocated by the first one-context FairBottleneck solve)
   // resident System mirror (lmmhip_res_*, lmm_resident_kernels.hpp): outlives uploads, freed with the
   // context.  Mirror arrays (res_own: the nine arrays of `res`, in its order) keep their contents when they grow;
   // scratch buffers do not.

@@ -6,6 +6,7 @@
 #include <cfloat>
 #include <climits>
 #include <cstdint>
+#include <type_traits>
 
 namespace lmmdev {
 
@@ -139,12 +140,16 @@ struct Dev {
   // constraints share no alive variable, so only a duplicate inside one constraint could claim twice.
   uint8_t* cdup;
   // per-variable state
+  // (Member order matters here: a kernel loads adjacent arguments it uses as one wider scalar load.  Three diagnostic
+  // members keep hot ones apart that were apart before the engines' fields left — anat between x and vstate, anat_r
+  // between vstate and ratio, flagbits between ctl and vstat — which leaves the round kernels' loads, and the SGPR
+  // spills of mm_persist, as they were.  tests/test_dev_views.py pins these adjacencies.)
   double* x;        // [nV] values (output)
-  int32_t* fixr;    // [nV] fair bottleneck: last round the variable was listed (measurement only)
+  // round anatomy (diagnostic build LMM_ANAT=1 only, else null): per-wave stamps of the round engine's kernels in
+  // the rounds anat_r[0..kAnatSlots) (the Anat probe below)
+  unsigned long long* anat;
   int32_t* vstate;  // [nV] maxmin: 0 alive, r+1 = fixed or dropped in round r (claimed with atomicCAS)
-  double* vtmp;     // [nV] fair bottleneck: mu
-  uint8_t* vst;     // [nV] fair bottleneck: 1 listed / 0 not
-  uint32_t* vstb;   // [nV/32 + 1] fair bottleneck: vst packed 32 per word for fbk_count (fb_pack_vst)
+  int32_t anat_r[4];
   // per-constraint state
   double* ratio;    // [nC] remaining/usage, +inf when out of the light table
   uint16_t* key;    // [nC] round-down 16-bit key of ratio, kDeadKey when out
@@ -170,7 +175,48 @@ struct Dev {
   int32_t* rtgt[3];  // per row: constraint the variable votes for; kUnvoted / kRetired
   uint16_t* skey[3];  // per row: min key over the row's OTHER constraints at its last vote (0 if bounded)
   int32_t* bsum;    // compaction scratch: per-block rows / elems (2 x blocks)
-  // fair bottleneck: CSC chunks (lmm_fb_kernels.hpp) and the per-constraint exchange buffers
+  // The next five are the round engine's modes.  solve_maxmin fills them in its own copy of the Dev (round_buffers);
+  // the context's Dev (lmmhip_ctx::d) never carries them — they are null there for its whole life — so no other
+  // engine, getter or fallback re-run can see a stale one.  They stay here, not in a view of their own like the
+  // frontier's and FairBottleneck's fields below: their readers (vote_row, vote_waves, update_groups, init_vars_range,
+  // the compactions) are shared with the persistent kernel, and would have to be templates on the view type.
+  int32_t* rdq[2];   // round engine, short rows (LMMHIP_RDQ): constraints the vote made ready, by round parity
+  int32_t* rqst;     // [nC] the round a constraint was last queued for (one entry per constraint and round)
+  int32_t* useg;     // [blocks x kUSeg] the update's ready candidates for the next round, a segment per workgroup
+  int32_t* ucnt;     // [blocks] their counts
+  RowRecs crec[3];   // round engine, short rows: per alive row one packed record (vote_row), in the solve's form
+  int32_t* ctl;     // control words
+  uint64_t* flagbits;  // [nC/64 + 2] measurement only: targets of the rows the filter queued (kDiag)
+  int32_t* vstat;   // profiling only (else null): [round][block] re-evaluated rows / elements
+};
+
+// What a single engine's kernels see beside the Dev.  A kernel takes the system by value as a Dev (the round,
+// persistent and batch engines, the getters), or as the view of its engine: FrDev (fr_*) or FbDev (fb_*, fbk_*, fbo_*,
+// fbp_*).  No kernel can name another engine's fields, and the context's Dev carries none of them, so there is nothing
+// to null after a solve.  Helpers that take `const Dev&` accept a view through its base.
+
+// Frontier engine (lmm_frontier_kernels.hpp): votes registered at their target constraint.  All of one solve:
+// solve_maxmin_frontier fills them from the FrontierEngine's scratch buffers.
+struct FrFields {
+  const int2* csr_cs;        // [nnz] per CSR element: its constraint and its CSC position (one 8-B pair)
+  double2* pvb;              // [nV] per variable: (bound, penalty) of this solve, one 16-B record
+  uint32_t* key32;           // [nC] 32-bit key of the ratio (ratio_key32), kDead32 when out of the light table
+  uint32_t* vslot;           // [nnz] per CSC element: floor of the vote registered there, kNoVoter if none
+  uint32_t* minfl;           // [nC] lower bound of the floors registered at the constraint (kNoVoter: none)
+  unsigned long long* fq_a;  // [nnz] re-vote queue, one segment per fr_update workgroup: variable | target << 32
+  unsigned long long* fq_b;  // [nnz]   and the variable's CSR row (begin | end << 32)
+  int32_t* fq_n;             // [nC / kFB + 1] queued variables per segment
+};
+
+// FairBottleneck (lmm_fb_kernels.hpp).  The FairEngine (lmm_ctx.hpp) keeps the fields that outlive a call — all but
+// hprog; a solve, and each call of the sharded protocol, launches with a view built from them.
+struct FbFields {
+  // per-variable state
+  int32_t* fixr;    // [nV] last round the variable was listed (measurement only)
+  double* vtmp;     // [nV] mu
+  uint8_t* vst;     // [nV] 1 listed / 0 not
+  uint32_t* vstb;   // [nV/32 + 1] vst packed 32 per word for fbk_count (fb_pack_vst)
+  // CSC chunks and the per-constraint exchange buffers
   int32_t nch;               // number of chunks
   const int32_t* ch_cnst;    // [nch] constraint of each chunk
   const uint32_t* ch_beg;    // [nch] first CSC element of each chunk
@@ -187,35 +233,16 @@ struct Dev {
   int32_t* vperm;            // [nV] position of each variable in the locality order
   int32_t* csc_vp;           // [nnz] csc_v through vperm
   double* mu_p;              // [nV] mu (vtmp) in the locality order
-  uint64_t* flagbits;  // [nC/64 + 2] measurement only: targets of the rows the filter queued (kDiag)
-  // frontier engine (lmm_frontier_kernels.hpp): votes registered at their target constraint
-  const int2* csr_cs;        // [nnz] per CSR element: its constraint and its CSC position (one 8-B pair)
-  double2* pvb;              // [nV] per variable: (bound, penalty) of this solve, one 16-B record
-  uint32_t* key32;           // [nC] 32-bit key of the ratio (ratio_key32), kDead32 when out of the light table
-  uint32_t* vslot;           // [nnz] per CSC element: floor of the vote registered there, kNoVoter if none
-  uint32_t* minfl;           // [nC] lower bound of the floors registered at the constraint (kNoVoter: none)
-  unsigned long long* fq_a;  // [nnz] re-vote queue, one segment per fr_update workgroup: variable | target << 32
-  unsigned long long* fq_b;  // [nnz]   and the variable's CSR row (begin | end << 32)
-  int32_t* fq_n;             // [nC / kFB + 1] queued variables per segment
-  // The next five are the round engine's modes.  solve_maxmin fills them in its own copy of the Dev (round_buffers);
-  // the context's Dev (lmmhip_ctx::d) never carries them — they are null there for its whole life — so no other
-  // engine, getter or fallback re-run can see a stale one.
-  int32_t* rdq[2];   // round engine, short rows (LMMHIP_RDQ): constraints the vote made ready, by round parity
-  int32_t* rqst;     // [nC] the round a constraint was last queued for (one entry per constraint and round)
-  int32_t* useg;     // [blocks x kUSeg] the update's ready candidates for the next round, a segment per workgroup
-  int32_t* ucnt;     // [blocks] their counts
-  RowRecs crec[3];   // round engine, short rows: per alive row one packed record (vote_row), in the solve's form
-  int32_t* ctl;     // control words
   // one-context FairBottleneck: pinned host words fbk_share writes itself (system scope) — [0] rounds started, [1] 1
   // once the solve is over — by which the host paces its rounds without a control-word copy kernel per round
-  // (solve_fair_rounds).  Null elsewhere (the max-min engines, the sharded FairBottleneck phases)
+  // (solve_fair_rounds).  Null in the views of the polled loop and of the sharded phases
   int32_t* hprog;
-  int32_t* vstat;   // profiling only (else null): [round][block] re-evaluated rows / elements
-  // round anatomy (diagnostic build LMM_ANAT=1 only, else null): per-wave stamps of the round engine's kernels in
-  // the rounds anat_r[0..kAnatSlots) (the Anat probe below)
-  unsigned long long* anat;
-  int32_t anat_r[4];
 };
+
+struct FrDev : Dev, FrFields {};  // (aggregates: FrDev{dev, fields})
+struct FbDev : Dev, FbFields {};
+static_assert(std::is_trivially_copyable<FrDev>::value && std::is_trivially_copyable<FbDev>::value,
+              "the views are kernel arguments");
 
 // Alive-row variable ids carry the variable's "bounded" flag in the sign bit (set at every solve's init),
 // so the re-vote of an unbounded variable skips its bound and penalty gathers.

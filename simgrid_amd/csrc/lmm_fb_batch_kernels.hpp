@@ -58,7 +58,7 @@ constexpr int kFBB = 256;  // threads per workgroup
 // WL: the weights staged in LDS (behind the per-variable doubles), else read from csr_w / csc_w.
 template <bool WL>
 __global__ void __launch_bounds__(kFBB, 6)
-    fbk_batch_lds(Dev s, const int64_t* __restrict__ var_off, const int64_t* __restrict__ cnst_off, int64_t nsys,
+    fbk_batch_lds(FbDev s, const int64_t* __restrict__ var_off, const int64_t* __restrict__ cnst_off, int64_t nsys,
                   double prec, int max_nv, int max_nc, int max_nnz, int max_rounds, int32_t* block_rounds) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   double* c_rem = reinterpret_cast<double*>(lds);

@@ -20,7 +20,7 @@
 
 namespace lmmdev {
 
-__global__ void __launch_bounds__(kBlock) fb_init(Dev s) {
+__global__ void __launch_bounds__(kBlock) fb_init(FbDev s) {
   const int64_t n = s.nV > s.nC ? s.nV : s.nC;
   for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += int64_t(gridDim.x) * kBlock) {
     if (i < s.nV) {  // fair_bottleneck.cpp:29-41 (only listed variables are flattened)
@@ -42,14 +42,14 @@ __global__ void __launch_bounds__(kBlock) fb_init(Dev s) {
     s.ctl[CTL_ANY0] = s.nV > 0;
 }
 
-__device__ __forceinline__ uint32_t chunk_end(const Dev& s, int q, int c) {
+__device__ __forceinline__ uint32_t chunk_end(const FbDev& s, int q, int c) {
   const uint32_t e = s.ch_beg[q] + kFbChunk, ce = s.cnst_ptr[c + 1];
   return e < ce ? e : ce;
 }
 
 // The listed flags packed 32 per word (vstb) before the count: its gathers then hit a table of nV / 8 bytes
 // (1.25 MB at C5's 10^7 flows: resident in every XCD's L2) instead of the nV-byte flags.
-__global__ void __launch_bounds__(kBlock) fb_pack_vst(Dev s) {
+__global__ void __launch_bounds__(kBlock) fb_pack_vst(FbDev s) {
   if (s.ctl[CTL_DONE])
     return;
   const int64_t nw = (int64_t(s.nV) + 31) / 32;
@@ -72,7 +72,7 @@ __global__ void __launch_bounds__(kBlock) fb_pack_vst(Dev s) {
 
 // :67-74 — listed variables (w > 0: every flattened element) of each chunk of a listed constraint.  all = 1
 // (round 0: fair_bottleneck.cpp:29-41 lists every flattened variable): the chunk's length, nothing gathered.
-__global__ void __launch_bounds__(kBlock) fbk_count(Dev s, int all) {
+__global__ void __launch_bounds__(kBlock) fbk_count(FbDev s, int all) {
   if (s.ctl[CTL_DONE])
     return;
   const int lane = threadIdx.x & (kWave - 1);
@@ -105,7 +105,7 @@ __global__ void __launch_bounds__(kBlock) fbk_count(Dev s, int all) {
 }
 
 // per constraint: chunk counts -> xnb[c]; xnb[nC] = "a variable of this shard is still listed"
-__global__ void __launch_bounds__(kBlock) fbk_nb(Dev s, int par) {
+__global__ void __launch_bounds__(kBlock) fbk_nb(FbDev s, int par) {
   if (s.ctl[CTL_DONE])
     return;
   for (int c = blockIdx.x * kBlock + threadIdx.x; c < s.nC; c += gridDim.x * kBlock) {
@@ -120,7 +120,7 @@ __global__ void __launch_bounds__(kBlock) fbk_nb(Dev s, int par) {
 
 // Per-wave sum of work counter k into one of its kFbwSlots slots (one atomic per wave, the waves spread over the slots;
 // lmmhip_fb_work sums them).
-__device__ __forceinline__ void fb_work_add(const Dev& s, int k, unsigned long long v) {
+__device__ __forceinline__ void fb_work_add(const FbDev& s, int k, unsigned long long v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1)
     v += __shfl_xor(v, o, kWave);
@@ -131,7 +131,7 @@ __device__ __forceinline__ void fb_work_add(const Dev& s, int k, unsigned long l
 
 // :65-87 — usage = remaining / nb (FATPIPE: nb -> 1); nb == 0 erases the constraint.  xnb holds the
 // counts of every shard; xnb[nC] == 0 means no variable is listed anywhere: the solve is over (:145).
-__global__ void __launch_bounds__(kBlock) fbk_share(Dev s, int par) {
+__global__ void __launch_bounds__(kBlock) fbk_share(FbDev s, int par) {
   if (s.ctl[CTL_DONE])
     return;
   if (s.xnb[s.nC] == 0) {
@@ -172,7 +172,7 @@ __global__ void __launch_bounds__(kBlock) fbk_share(Dev s, int par) {
 // :89-105 — per listed variable: mu = min(usage/w, bound - value); value += mu; exact
 // `value == bound` drops it from the list.
 // :89-105 once the minimum of usage / w over the row is known: bound, value, exact `value == bound` delisting.
-__device__ __forceinline__ int var_inc_finish(const Dev& s, int64_t v, double inc, int round) {
+__device__ __forceinline__ int var_inc_finish(const FbDev& s, int64_t v, double inc, int round) {
   const double vb = s.vbound[v];
   double x = s.x[v];
   if (vb > 0)
@@ -194,7 +194,7 @@ __device__ __forceinline__ int var_inc_finish(const Dev& s, int64_t v, double in
 // read that range coalesced (the u-th element of 64 rows per load touched ~64 lines) and min-reduce each
 // element's usage / w into its row's slot in LDS (64-bit atomic min of the non-negative doubles' bits: the
 // same minimum as a sequential fmin).
-__global__ void __launch_bounds__(kBlock) fb_var_inc(Dev s, int par, int round) {
+__global__ void __launch_bounds__(kBlock) fb_var_inc(FbDev s, int par, int round) {
   if (s.ctl[CTL_DONE])
     return;
   __shared__ unsigned long long mn[kBlock];
@@ -283,7 +283,7 @@ __global__ void __launch_bounds__(kBlock) fb_var_inc(Dev s, int par, int round) 
 }
 
 // mu of CSC element j (variable v): from the locality-ordered copy when there is one (fb_perm).
-__device__ __forceinline__ double fb_mu(const Dev& s, uint32_t j, int32_t v) {
+__device__ __forceinline__ double fb_mu(const FbDev& s, uint32_t j, int32_t v) {
   return s.mu_p ? s.mu_p[s.csc_vp[j]] : s.vtmp[v];
 }
 
@@ -292,7 +292,7 @@ __device__ __forceinline__ double fb_mu(const Dev& s, uint32_t j, int32_t v) {
 // puts the flows a link carries in few runs; the chains, which must visit a link's elements in the reference's
 // order, then gather mu from a few regions instead of one line per element.  Values never move: only the
 // copy of mu the chains read (mu_p) and the element -> position map (csc_vp) use the order.
-__global__ void __launch_bounds__(kBlock) fbp_keys(Dev s, unsigned long long* key, int32_t* val) {
+__global__ void __launch_bounds__(kBlock) fbp_keys(FbDev s, unsigned long long* key, int32_t* val) {
   for (int64_t v = int64_t(blockIdx.x) * kBlock + threadIdx.x; v < s.nV; v += int64_t(gridDim.x) * kBlock) {
     const uint32_t b = s.var_ptr[v], e = s.var_ptr[v + 1];
     key[v] = b < e ? (unsigned long long)uint32_t(s.csr_c[b]) * uint64_t(s.nC) + uint32_t(s.csr_c[e - 1])
@@ -300,11 +300,11 @@ __global__ void __launch_bounds__(kBlock) fbp_keys(Dev s, unsigned long long* ke
     val[v] = int32_t(v);
   }
 }
-__global__ void __launch_bounds__(kBlock) fbp_inv(Dev s, const int32_t* order) {
+__global__ void __launch_bounds__(kBlock) fbp_inv(FbDev s, const int32_t* order) {
   for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < s.nV; i += int64_t(gridDim.x) * kBlock)
     s.vperm[order[i]] = int32_t(i);
 }
-__global__ void __launch_bounds__(kBlock) fbp_csc(Dev s) {
+__global__ void __launch_bounds__(kBlock) fbp_csc(FbDev s) {
   for (int64_t j = int64_t(blockIdx.x) * kBlock + threadIdx.x; j < s.nnz; j += int64_t(gridDim.x) * kBlock)
     s.csc_vp[j] = s.vperm[s.csc_v[j]];
 }
@@ -318,7 +318,7 @@ __global__ void __launch_bounds__(kBlock) fbp_csc(Dev s) {
 // fb_var_inc.
 // Shared constraints shorter than `longmin` elements take their increments in fbk_update_seq itself (fb_chain_pull);
 // only the long ones, whose chains are the round's critical path, get them precomputed here.
-__global__ void __launch_bounds__(kBlock) fbk_acc(Dev s, int all, uint32_t longmin) {  // all: round 0, every variable listed
+__global__ void __launch_bounds__(kBlock) fbk_acc(FbDev s, int all, uint32_t longmin) {  // all: round 0, every variable listed
   if (s.ctl[CTL_DONE])
     return;
   const int lane = threadIdx.x & (kWave - 1);
@@ -366,7 +366,7 @@ __global__ void __launch_bounds__(kBlock) fbk_acc(Dev s, int all, uint32_t longm
 }
 
 // per FATPIPE constraint: chunk minima in chunk order -> xmin
-__global__ void __launch_bounds__(kBlock) fbk_accc(Dev s) {
+__global__ void __launch_bounds__(kBlock) fbk_accc(FbDev s) {
   if (s.ctl[CTL_DONE])
     return;
   for (int c = blockIdx.x * kBlock + threadIdx.x; c < s.nC; c += gridDim.x * kBlock) {
@@ -380,7 +380,7 @@ __global__ void __launch_bounds__(kBlock) fbk_accc(Dev s) {
 
 // :118-125 — FATPIPE: usage = min(usage, w * mu over the enabled elements) (an enabled zero-weight element,
 // cflags bit1, gives 0), remaining -= usage, clamped (double_update, surf_interface.hpp:34-44)
-__device__ __forceinline__ double fb_fat_update(const Dev& s, int64_t c, double rem, double elem_min, double prec,
+__device__ __forceinline__ double fb_fat_update(const FbDev& s, int64_t c, double rem, double elem_min, double prec,
                                                 double* use_out) {
   double u = s.use[c];
   if (s.cflags[c] & 2)
@@ -578,7 +578,7 @@ __device__ __forceinline__ double fb_chain(const double* __restrict__ fbd, uint3
 // fb_chain with the increments computed on the fly, w * mu for EVERY element of the constraint (a delisted
 // variable's mu, vtmp, is the one of its last listed round: the same product fbk_acc would have kept in fbd):
 // the element loads run two batches ahead and the mu gathers one batch ahead of the chain.
-__device__ __forceinline__ double fb_chain_pull(const Dev& s, uint32_t cb, uint32_t ce, double rem, double prec,
+__device__ __forceinline__ double fb_chain_pull(const FbDev& s, uint32_t cb, uint32_t ce, double rem, double prec,
                                                 double* d, int lane) {
   int32_t ix[kSeqP];
   double ww[kSeqP], vt[kSeqP];
@@ -630,7 +630,7 @@ __device__ __forceinline__ double fb_chain_pull(const Dev& s, uint32_t cb, uint3
 // are the round's critical path, so each gets a whole workgroup (`fb_long_chain`) instead of one wave:
 // fb_chain_scan's argument over steps of kBlock x 8 = 2048 increments, the int64 prefix a block-wide scan.
 // The list (fb_long[0] = count, then the constraint ids) is built once per solve by fb_long_list.
-__global__ void __launch_bounds__(kBlock) fb_long_list(Dev s, uint32_t longmin) {
+__global__ void __launch_bounds__(kBlock) fb_long_list(FbDev s, uint32_t longmin) {
   for (int64_t c = int64_t(blockIdx.x) * kBlock + threadIdx.x; c < s.nC; c += int64_t(gridDim.x) * kBlock)
     if (!(s.cflags[c] & 1) && s.cnst_ptr[c + 1] - s.cnst_ptr[c] >= longmin)
       s.fb_long[1 + atomicAdd(&s.fb_long[0], 1)] = int32_t(c);
@@ -682,7 +682,7 @@ __device__ __forceinline__ int fb_block_min(int v, int* wi) {
 // The chain of long shared constraint c by the whole workgroup (sh: kBlock * kSeqP doubles of LDS).  Bit for
 // bit the reference's loop, as fb_chain: non-negative steps are chained by the binade scan (exits and ties as
 // fp64 steps, the end clamp once per step), anything else by thread 0 one double_update at a time.
-__device__ void fb_long_chain(const Dev& s, int32_t c, double prec, double* sh) {
+__device__ void fb_long_chain(const FbDev& s, int32_t c, double prec, double* sh) {
   __shared__ long long ws[kBlock / kWave];
   __shared__ int wi[kBlock / kWave];
   __shared__ double bx[2];
@@ -809,7 +809,7 @@ __device__ void fb_long_chain(const Dev& s, int32_t c, double prec, double* sh) 
 // longest first from a queue (LMMHIP_FB_LPT): 8.38 vs 8.35-8.37 ms on C5, removed in round 6.  Round 6 measured the
 // constraint's ratio / remaining loaded with its flags before the erased-flag store, with fb_var_inc's bound / value
 // loaded with the listed flags: 8.40-8.41 against 8.36-8.37, not kept.
-__global__ void __launch_bounds__(kBlock) fbk_update_seq(Dev s, double prec, uint32_t longmin, int nlb) {
+__global__ void __launch_bounds__(kBlock) fbk_update_seq(FbDev s, double prec, uint32_t longmin, int nlb) {
   if (s.ctl[CTL_DONE])
     return;
   __shared__ __attribute__((aligned(16))) double dl[kBlock / kWave][kSeqP * kWave];
@@ -873,7 +873,7 @@ __global__ void __launch_bounds__(kBlock) fbk_update_seq(Dev s, double prec, uin
 
 // phase 1 tail: this shard's mu into its block of the gathered vector (a delisted variable keeps its
 // last mu: its increment still counts, fair_bottleneck.cpp:111-116)
-__global__ void __launch_bounds__(kBlock) fbo_put_mu(Dev s, FbOwner o) {
+__global__ void __launch_bounds__(kBlock) fbo_put_mu(FbDev s, FbOwner o) {
   if (s.ctl[CTL_DONE])
     return;
   for (int64_t v = int64_t(blockIdx.x) * kBlock + threadIdx.x; v < s.nV; v += int64_t(gridDim.x) * kBlock)
@@ -885,7 +885,7 @@ __global__ void __launch_bounds__(kBlock) fbo_put_mu(Dev s, FbOwner o) {
 // changed this round: a delisted variable's mu is constant (fair_bottleneck.cpp:89-105 runs over the list
 // only).  Appended in any order (one atomic per wave on *cnt, zeroed by the caller); the receiving ranks
 // scatter them into their copy of xmu.
-__global__ void __launch_bounds__(kBlock) fbo_pack_mu(Dev s, FbOwner o, int all, int32_t* pos, double* mu,
+__global__ void __launch_bounds__(kBlock) fbo_pack_mu(FbDev s, FbOwner o, int all, int32_t* pos, double* mu,
                                                       int32_t* cnt) {
   if (s.ctl[CTL_DONE])
     return;
@@ -902,7 +902,7 @@ __global__ void __launch_bounds__(kBlock) fbo_pack_mu(Dev s, FbOwner o, int all,
 
 // phase 2a: increments of the owned listed constraints' elements (every element: the gathered mu of a
 // delisted variable is its last one), one wave per chunk
-__global__ void __launch_bounds__(kBlock) fbo_acc(Dev s, FbOwner o) {
+__global__ void __launch_bounds__(kBlock) fbo_acc(FbDev s, FbOwner o) {
   if (s.ctl[CTL_DONE])
     return;
   const int lane = threadIdx.x & (kWave - 1);
@@ -932,7 +932,7 @@ __global__ void __launch_bounds__(kBlock) fbo_acc(Dev s, FbOwner o) {
 
 // phase 2b: one wave per owned constraint: its new remaining (listed: the chain / FATPIPE update; else
 // unchanged) into xrem
-__global__ void __launch_bounds__(kBlock) fbo_chain(Dev s, FbOwner o, double prec) {
+__global__ void __launch_bounds__(kBlock) fbo_chain(FbDev s, FbOwner o, double prec) {
   if (s.ctl[CTL_DONE])
     return;
   __shared__ __attribute__((aligned(16))) double dl[kBlock / kWave][kSeqP * kWave];
@@ -960,7 +960,7 @@ __global__ void __launch_bounds__(kBlock) fbo_chain(Dev s, FbOwner o, double pre
 }
 
 // phase 3a: every listed constraint takes its owner's remaining; remaining <= 0 erases it (:129-131)
-__global__ void __launch_bounds__(kBlock) fbo_apply(Dev s, FbOwner o) {
+__global__ void __launch_bounds__(kBlock) fbo_apply(FbDev s, FbOwner o) {
   if (s.ctl[CTL_DONE])
     return;
   for (int c = blockIdx.x * kBlock + threadIdx.x; c < s.nC; c += gridDim.x * kBlock) {
@@ -977,7 +977,7 @@ __global__ void __launch_bounds__(kBlock) fbo_apply(Dev s, FbOwner o) {
 }
 
 // :132-139 — the listed variables of an erased constraint leave the list
-__global__ void __launch_bounds__(kBlock) fbk_unlist(Dev s, int bits) {
+__global__ void __launch_bounds__(kBlock) fbk_unlist(FbDev s, int bits) {
   if (s.ctl[CTL_DONE])
     return;
   const int lane = threadIdx.x & (kWave - 1);

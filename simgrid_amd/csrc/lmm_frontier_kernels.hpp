@@ -46,7 +46,7 @@ constexpr int kFVS = 4;                  // fr_update segments (workgroups) per 
 // CSR element -> (constraint, CSC position) pairs (csr_cs), once per uploaded structure: one wave per
 // constraint, each CSC element finds its CSR element in its variable's row (csc_row); the k-th element of a
 // variable on a constraint maps to the k-th (duplicates: cdup).  Also the largest CSC degree (into *maxdeg).
-__global__ void __launch_bounds__(kBlock) fr_c2s(Dev s, int2* cs, int32_t* maxdeg) {
+__global__ void __launch_bounds__(kBlock) fr_c2s(FrDev s, int2* cs, int32_t* maxdeg) {
   const int lane = threadIdx.x & (kWave - 1);
   int md = 0;
   for (int64_t c = (int64_t(blockIdx.x) * kBlock + threadIdx.x) / kWave; c < s.nC;
@@ -89,7 +89,7 @@ __global__ void __launch_bounds__(kBlock) fr_c2s(Dev s, int2* cs, int32_t* maxde
 
 // Per-solve variable state (mm_init_vars) + the (bound, penalty) record the re-votes read in one line.
 // (with the slots' and floors' kNoVoter fill: two copy-engine fills and their launch gaps less per solve)
-__global__ void __launch_bounds__(kBlock) fr_init_vars(Dev s) {
+__global__ void __launch_bounds__(kBlock) fr_init_vars(FrDev s) {
   const int64_t stride = int64_t(gridDim.x) * kBlock;
   for (int64_t v = int64_t(blockIdx.x) * kBlock + threadIdx.x; v < s.nV; v += stride) {
     s.x[v] = 0.0;
@@ -143,7 +143,7 @@ __device__ __forceinline__ uint32_t row_floor32(uint32_t sk, uint32_t mk, double
 // (an: the dependent levels: lv[1] row (csr_cs) + bound / penalty, lv[2] keys + floors, lv[3] the rest of the row +
 // exact ratios, lv[4] the vote's stores and atomics issued)
 template <int R, bool kMinfl = true, bool kEarly = true>
-__device__ __forceinline__ int fr_revote(const Dev& s, int v, int t, uint32_t b, uint32_t e, int round, Anat an) {
+__device__ __forceinline__ int fr_revote(const FrDev& s, int v, int t, uint32_t b, uint32_t e, int round, Anat an) {
   const uint32_t* __restrict__ key = s.key32;
   // (a queued variable is alive: votes are registered only by alive variables, and the slot of a variable
   // fixed since — at its bound, by fr_revote — was cleared when it was queued)
@@ -292,14 +292,14 @@ __device__ __forceinline__ int fr_revote(const Dev& s, int v, int t, uint32_t b,
 }
 
 // Round 0: every variable votes (the floors' per-constraint minima come after, from fr_minfl_all).
-__global__ void __launch_bounds__(kBlock) fr_vote_all(Dev s) {
+__global__ void __launch_bounds__(kBlock) fr_vote_all(FrDev s) {
   for (int64_t v = int64_t(blockIdx.x) * kBlock + threadIdx.x; v < s.nV; v += int64_t(gridDim.x) * kBlock)
     fr_revote<8, false>(s, int(v), kUnvoted, s.var_ptr[v], s.var_ptr[v + 1], 0, Anat());
 }
 
 // After round 0's vote: minfl[c] = min of the floors registered in c's slots, 16 lanes per constraint (four
 // constraints per wave; one segmented pass over the slots instead of ~nV atomics).
-__global__ void __launch_bounds__(kBlock) fr_minfl_all(Dev s) {
+__global__ void __launch_bounds__(kBlock) fr_minfl_all(FrDev s) {
   const int lane = threadIdx.x & (kWave - 1), gl = lane & 15;
   const int64_t wave = (int64_t(blockIdx.x) * kBlock + threadIdx.x) / kWave;
   const int64_t nwaves = int64_t(gridDim.x) * (kBlock / kWave);
@@ -326,7 +326,7 @@ __global__ void __launch_bounds__(kBlock) fr_minfl_all(Dev s) {
 // fr_vote_blk: the work of workgroup vb (an: lv[0] the queue counts; counters 0 queued rows of the workgroup, 1 this
 // lane's re-votes; ar: lv[0] a queue entry, then fr_revote's levels).
 template <int R>
-__device__ __forceinline__ void fr_vote_blk(const Dev& s, int round, int spb, int vb, Anat an, Anat ar) {
+__device__ __forceinline__ void fr_vote_blk(const FrDev& s, int round, int spb, int vb, Anat an, Anat ar) {
   // spb (<= kFVS) consecutive segments per workgroup: on C2 ~170 queued rows, one pass, and the launch's
   // workgroups resident at once; small systems keep one segment per workgroup (more workgroups)
   const int64_t nseg = (int64_t(s.nC) + kFB - 1) / kFB;
@@ -362,7 +362,7 @@ __device__ __forceinline__ void fr_vote_blk(const Dev& s, int round, int spb, in
   }
 }
 
-template <int R = 8> __global__ void __launch_bounds__(kFB) fr_vote(Dev s, int round, int spb) {
+template <int R = 8> __global__ void __launch_bounds__(kFB) fr_vote(FrDev s, int round, int spb) {
   AnatWave aw, awr;  // (the workgroup's queue; the lane's re-votes)
   const Anat an = aw.open(s, round, ANAT_VOTE), ar = awr.open(s, round, ANAT_VOTE);
   const unsigned long long t_in = an.restart();
@@ -414,7 +414,7 @@ constexpr int kFrSatU = 8;
 // (an: the chunk's dependent levels: lv[2] CSC elements + variable states, lv[3] the claimed rows' elements, lv[4]
 // their constraints' words, lv[5] the pushes issued, lv[6] the claims / values stored; counters 1 chunks, 2 fixed
 // variables, 3 pushed elements)
-__device__ __forceinline__ void fr_sat_chunk(const Dev& s, int32_t c, double r, uint32_t j0, uint32_t cend,
+__device__ __forceinline__ void fr_sat_chunk(const FrDev& s, int32_t c, double r, uint32_t j0, uint32_t cend,
                                              int round, int lane, int* pre, bool dup, Anat an) {
   an.restart();
   an.count(1);
@@ -549,7 +549,7 @@ template <int NB> struct FrSatLds {
 };
 
 template <int NB>
-__device__ __forceinline__ void fr_flush(const Dev& s, int round, FrSatLds<NB>& L, Anat an) {
+__device__ __forceinline__ void fr_flush(const FrDev& s, int round, FrSatLds<NB>& L, Anat an) {
   constexpr int NBW = NB / kWave;
   const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
   const int ta = L.na, tb = L.nb;
@@ -574,7 +574,7 @@ __device__ __forceinline__ void fr_flush(const Dev& s, int round, FrSatLds<NB>& 
 constexpr int kFS = 1024;
 
 template <int NB>
-__device__ __forceinline__ void fr_sat_blk(const Dev& s, int round, int bigch, int vb, FrSatLds<NB>& L,
+__device__ __forceinline__ void fr_sat_blk(const FrDev& s, int round, int bigch, int vb, FrSatLds<NB>& L,
                                            Anat an) {
   constexpr int NBW = NB / kWave;
   const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
@@ -657,7 +657,7 @@ __device__ __forceinline__ void fr_sat_blk(const Dev& s, int round, int bigch, i
     fr_flush<NB>(s, round, L, an);
 }
 
-template <int kFS> __global__ void __launch_bounds__(kFS) fr_sat(Dev s, int round, int bigch) {
+template <int kFS> __global__ void __launch_bounds__(kFS) fr_sat(FrDev s, int round, int bigch) {
   AnatWave aw;  // (counters: the workgroup's chunks, this wave's chunks, fixed variables, pushed elements)
   const Anat an = aw.open(s, round, ANAT_SAT);
   const unsigned long long t_in = an.restart();
@@ -679,7 +679,7 @@ template <int kFS> __global__ void __launch_bounds__(kFS) fr_sat(Dev s, int roun
 // The big ready constraints listed by fr_sat (count CTL_NREADY, reset by fr_update): kFrBigWaves waves per
 // constraint over the whole grid, wave k taking chunks k, k + kFrBigWaves, ...
 // (the grid's waves over the list: wave / nwaves; wpre = the calling wave's 64-int LDS scratch)
-__device__ __forceinline__ void fr_sat_big_waves(const Dev& s, int round, int bigw, int nb, int64_t wave,
+__device__ __forceinline__ void fr_sat_big_waves(const FrDev& s, int round, int bigw, int nb, int64_t wave,
                                                  int64_t nwaves, int* wpre, Anat an) {
   const int lane = threadIdx.x & (kWave - 1);
   for (int64_t g = wave; g < int64_t(nb) * bigw; g += nwaves) {
@@ -695,7 +695,7 @@ __device__ __forceinline__ void fr_sat_big_waves(const Dev& s, int round, int bi
   }
 }
 
-__global__ void __launch_bounds__(kBlock) fr_sat_big(Dev s, int round, int bigw) {
+__global__ void __launch_bounds__(kBlock) fr_sat_big(FrDev s, int round, int bigw) {
   AnatWave aw;
   const Anat an = aw.open(s, round, ANAT_SATB);
   const unsigned long long t_in = an.restart();
@@ -747,7 +747,7 @@ struct FrUpdLds {
 // slots, lv[4] queued voters' variable and row, lv[5] stores + barriers; counter 0 scanned slots)
 // spec (round 6, small systems): a constraint's record, scales, votes, floor and CSC range are loaded with its key and
 // touch flag whether or not it was touched (coalesced, one constraint per lane), one dependent level instead of two.
-__device__ __forceinline__ void fr_update_blk(const Dev& s, int round, double prec, int vb, FrUpdLds& U, bool spec,
+__device__ __forceinline__ void fr_update_blk(const FrDev& s, int round, double prec, int vb, FrUpdLds& U, bool spec,
                                               Anat an) {
   int& qn = U.qn;
   auto& pre = U.pre;
@@ -960,7 +960,7 @@ __device__ __forceinline__ void fr_update_blk(const Dev& s, int round, double pr
   an.level(5, 0u);
 }
 
-__global__ void __launch_bounds__(kFB) fr_update(Dev s, int round, double prec, int spec) {
+__global__ void __launch_bounds__(kFB) fr_update(FrDev s, int round, double prec, int spec) {
   AnatWave aw;
   const Anat an = aw.open(s, round, ANAT_UPD);
   const unsigned long long t_in = an.restart();

@@ -15,9 +15,9 @@
 #include "lmm_scan.hpp"
 
 void free_owner(lmmhip_ctx* c) {
-  c->fbo_allocs.clear();
-  c->fbo = FbOwner{};
-  c->fbo_ready = false;
+  c->fair.owner_allocs.clear();
+  c->fair.owner = FbOwner{};
+  c->fair.owner_ready = false;
 }
 
 static void free_all(lmmhip_ctx* c) {
@@ -25,10 +25,9 @@ static void free_all(lmmhip_ctx* c) {
   free_owner(c);
   c->d = Dev{};
   c->uploaded = false;
-  c->xnb_own = nullptr;
-  c->xmin_own = nullptr;
-  c->fbd_cap = 0;
-  c->fb_shard = false;
+  c->fair.f = FbFields{};
+  c->fair.fbd_cap = 0;
+  c->fair.shard_xnb = nullptr;
   c->res_flat = false;
 }
 
@@ -103,6 +102,7 @@ int lmmhip_ctx_destroy(lmmhip_ctx* c) {
 static int alloc_flat_exact(lmmhip_ctx* c, int64_t nV, int64_t nC, int64_t nnz, int64_t nch, FlatBufs* o) {
   free_all(c);
   Dev& d = c->d;
+  FbFields& f = c->fair.f;
   d.nV = int32_t(nV);
   d.nC = int32_t(nC);
   d.nnz = nnz;
@@ -126,10 +126,10 @@ static int alloc_flat_exact(lmmhip_ctx* c, int64_t nV, int64_t nC, int64_t nnz, 
   rc |= dalloc(c, &cb, nC);
   rc |= dalloc(c, &cf, nC);
   rc |= dalloc(c, &d.x, nV);
-  rc |= dalloc(c, &d.fixr, nV);
-  rc |= dalloc(c, &d.vtmp, nV);
-  rc |= dalloc(c, &d.vst, int64_t(nV) + 32);  // (+32: read 32 flags at a time by fb_pack_vst)
-  rc |= dalloc(c, &d.vstb, (int64_t(nV) + 31) / 32 + 1);
+  rc |= dalloc(c, &f.fixr, nV);
+  rc |= dalloc(c, &f.vtmp, nV);
+  rc |= dalloc(c, &f.vst, int64_t(nV) + 32);  // (+32: read 32 flags at a time by fb_pack_vst)
+  rc |= dalloc(c, &f.vstb, (int64_t(nV) + 31) / 32 + 1);
   rc |= dalloc(c, &d.ratio, nC);
   rc |= dalloc(c, &d.key, nC);
   rc |= dalloc(c, &d.rem, nC);
@@ -166,21 +166,19 @@ static int alloc_flat_exact(lmmhip_ctx* c, int64_t nV, int64_t nC, int64_t nnz, 
   rc |= dalloc(c, &chc, nch);
   rc |= dalloc(c, &chb, nch);
   rc |= dalloc(c, &cch, nC + 1);
-  rc |= dalloc(c, &d.pcnt, nch);
-  rc |= dalloc(c, &d.pacc, nch);
-  rc |= dalloc(c, &d.erased, nC);
-  rc |= dalloc(c, &c->xnb_own, nC + 1);
-  rc |= dalloc(c, &c->xmin_own, nC);
+  rc |= dalloc(c, &f.pcnt, nch);
+  rc |= dalloc(c, &f.pacc, nch);
+  rc |= dalloc(c, &f.erased, nC);
+  rc |= dalloc(c, &f.xnb, nC + 1);  // the context's own exchange buffers (a sharded solve brings its xnb)
+  rc |= dalloc(c, &f.xmin, nC);
   if (rc) {
     free_all(c);
     return LMMHIP_E_HIP;
   }
-  d.nch = int32_t(nch);
-  d.ch_cnst = chc;
-  d.ch_beg = chb;
-  d.c_ch = cch;
-  d.xnb = c->xnb_own;
-  d.xmin = c->xmin_own;
+  f.nch = int32_t(nch);
+  f.ch_cnst = chc;
+  f.ch_beg = chb;
+  f.c_ch = cch;
   d.var_ptr = vp;
   d.csr_c = csr_c;
   d.csr_w = csr_w;
@@ -226,13 +224,13 @@ int alloc_flat(lmmhip_ctx* c, int64_t nV, int64_t nC, int64_t nnz, int64_t nch, 
   } else {
     c->uploaded = false;
     c->res_flat = false;
-    c->fb_shard = false;
+    c->fair.shard_xnb = nullptr;
     free_owner(c);  // owned constraints refer to the previous system
   }
   c->d.nV = int32_t(nV);
   c->d.nC = int32_t(nC);
   c->d.nnz = nnz;
-  c->d.nch = int32_t(nch);
+  c->fair.f.nch = int32_t(nch);
   *o = c->fb_last;
   return 0;
 }
@@ -736,7 +734,7 @@ int lmmhip_round_profile(lmmhip_ctx* c, int64_t* alive_vars, int64_t* alive_elem
   HIPCHK(hipSetDevice(c->device));
   if (nV) {
     // maxmin: vstate = exit round + 1 (0 = never fixed); fair bottleneck: fixr = last listed round
-    const int32_t* src = c->last_kind == LMMHIP_KIND_MAXMIN ? c->d.vstate : c->d.fixr;
+    const int32_t* src = c->last_kind == LMMHIP_KIND_MAXMIN ? c->d.vstate : c->fair.f.fixr;
     HIPCHK(hipMemcpyAsync(fr.data(), src, sizeof(int32_t) * nV, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(vp.data(), c->d.var_ptr, sizeof(uint32_t) * (nV + 1), hipMemcpyDeviceToHost, c->stream));
   }

@@ -8,18 +8,19 @@
 #include "lmm_fb_kernels.hpp"
 #include "lmm_scan.hpp"
 
-static int fb_begin(lmmhip_ctx* c, double prec) {
-  Dev& d = c->d;
-  c->fb_round = 0;
-  c->fb_prec = prec;
+// The launches below take the view of the solve they belong to: solve_fair's (its long-constraint list, the locality
+// order and, paced, the progress words) or a sharded call's (shard_view).
+static int fb_begin(lmmhip_ctx* c, const FbDev& d, double prec) {
+  c->fair.round = 0;
+  c->fair.prec = prec;
   LAUNCH(0, -1, fb_init, grid_for(std::max(d.nV, d.nC), kBlock), kBlock, d);
   return 0;
 }
 
 // One phase of a fair-bottleneck round (lmm_fb_kernels.hpp); phase 2 ends the round.
-static int fb_phase(lmmhip_ctx* c, int phase) {
-  Dev& d = c->d;
-  const int64_t r = c->fb_round;
+static int fb_phase(lmmhip_ctx* c, const FbDev& d, int phase) {
+  FairEngine& e = c->fair;
+  const int64_t r = e.round;
   const int par = int(r & 1);
   const int gQ = grid_for(d.nch, kBlock / kWave);
   const int gC = grid_for(d.nC, kBlock);
@@ -34,31 +35,30 @@ static int fb_phase(lmmhip_ctx* c, int phase) {
   case 1:
     LAUNCH(3, r, fbk_share, gC, kBlock, d, par);
     LAUNCH(3, r, fb_var_inc, gV, kBlock, d, par, int(r));
-    if (c->fb_shard) {  // shards: this shard's mu into the gathered vector, then the caller's all-gather
-      LAUNCH(3, r, fbo_put_mu, gV, kBlock, d, c->fbo);
+    if (e.shard_xnb) {  // shards: this shard's mu into the gathered vector, then the caller's all-gather
+      LAUNCH(3, r, fbo_put_mu, gV, kBlock, d, e.owner);
       break;
     }
-    LAUNCH(4, r, fbk_acc, gQ, kBlock, d, int(r == 0), c->fb_longmin);
+    LAUNCH(4, r, fbk_acc, gQ, kBlock, d, int(r == 0), e.longmin);
     LAUNCH(4, r, fbk_accc, gC, kBlock, d);
     break;
   case 2:
-    if (c->fb_shard) {  // the owned constraints' chains from the gathered mu -> xrem (all-gathered)
-      LAUNCH(4, r, fbo_acc, grid_for(c->fbo.nch, kBlock / kWave), kBlock, d, c->fbo);
-      LAUNCH(5, r, fbo_chain, grid_for(c->fbo.nc, kBlock / kWave), kBlock, d, c->fbo, c->fb_prec);
+    if (e.shard_xnb) {  // the owned constraints' chains from the gathered mu -> xrem (all-gathered)
+      LAUNCH(4, r, fbo_acc, grid_for(e.owner.nch, kBlock / kWave), kBlock, d, e.owner);
+      LAUNCH(5, r, fbo_chain, grid_for(e.owner.nc, kBlock / kWave), kBlock, d, e.owner, e.prec);
       break;
     }
     // one context: element by element in the CSC order, bit-identical to the reference
-    LAUNCH(5, r, fbk_update_seq, c->fb_nlb + grid_for(d.nC, kBlock / kWave), kBlock, d, c->fb_prec,
-           c->fb_longmin, c->fb_nlb);
+    LAUNCH(5, r, fbk_update_seq, e.nlb + grid_for(d.nC, kBlock / kWave), kBlock, d, e.prec, e.longmin, e.nlb);
     LAUNCH(5, r, fbk_unlist, gQ, kBlock, d, int(r > 0));  // (vstb is packed in rounds > 0)
-    c->fb_round++;
+    e.round++;
     break;
   case 3:
-    if (!c->fb_shard)
+    if (!e.shard_xnb)
       return fail(LMMHIP_E_ARG, "phase 3 exists only in a sharded solve");
-    LAUNCH(5, r, fbo_apply, gC, kBlock, d, c->fbo);
+    LAUNCH(5, r, fbo_apply, gC, kBlock, d, e.owner);
     LAUNCH(5, r, fbk_unlist, gQ, kBlock, d, int(r > 0));  // (vstb is packed in rounds > 0)
-    c->fb_round++;
+    e.round++;
     break;
   default:
     return fail(LMMHIP_E_ARG, "fair-bottleneck phase must be 0..2 (one context) or 0..3 (shard)");
@@ -67,13 +67,11 @@ static int fb_phase(lmmhip_ctx* c, int phase) {
 }
 
 // The locality order of the one-context FairBottleneck's mu gathers (lmm_fb_kernels.hpp fbp_*): once per
-// uploaded system, outside the solve.  LMMHIP_FB_PERM=0 gathers mu by variable id instead (measurement knob).
-static int fb_perm(lmmhip_ctx* c) {
-  Dev& d = c->d;
-  if (!env_int("LMMHIP_FB_PERM", 1) || d.nV == 0) {
-    d.mu_p = nullptr;
+// uploaded system, outside the solve.  LMMHIP_FB_PERM=0 gathers mu by variable id instead (measurement knob): the
+// view's mu_p stays null.
+static int fb_perm(lmmhip_ctx* c, FbDev& d) {
+  if (!env_int("LMMHIP_FB_PERM", 1) || d.nV == 0)
     return 0;
-  }
   int32_t *v0, *v1;
   unsigned long long *k0, *k1;
   int rc = scratch(c, c->fair.k0, d.nV, &k0);
@@ -108,12 +106,12 @@ static int fb_perm(lmmhip_ctx* c) {
   return 0;
 }
 
-static int solve_fair_rounds(lmmhip_ctx* c, double prec) {
-  if (int rc = fb_begin(c, prec))
+static int solve_fair_rounds(lmmhip_ctx* c, FbDev& d, double prec) {
+  if (int rc = fb_begin(c, d, prec))
     return rc;
   // The reference's rounds are not bounded by the system size (FATPIPE remaining can shrink
   // geometrically: millions of rounds on 60-variable systems); give up past this budget.
-  const int64_t max_rounds = 64 * (int64_t(c->d.nV) + int64_t(c->d.nC)) + 4096;
+  const int64_t max_rounds = 64 * (int64_t(d.nV) + int64_t(d.nC)) + 4096;
   // (LMMHIP_FB_PACE=0) One round queued ahead of the termination poll: after round r the control words go to a pinned
   // slot (mm_ctl_out), round r + 1 is queued, then the host waits for round r's words.  A FairBottleneck round is
   // long (C5: 0.2-3 ms), so the GPU never waits on the host and at most one empty round (its launches return
@@ -129,11 +127,7 @@ static int solve_fair_rounds(lmmhip_ctx* c, double prec) {
     volatile int32_t* hp = c->h_ctl.p + 3 * CTL_WORDS;
     hp[0] = 0;
     hp[1] = 0;
-    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d.hprog), c->h_ctl.p + 3 * CTL_WORDS, 0));
-    struct HprogOff {  // (the context's Dev: the other engines and the sharded phases run without the words)
-      Dev& d;
-      ~HprogOff() { d.hprog = nullptr; }
-    } hprog_off{c->d};
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&d.hprog), c->h_ctl.p + 3 * CTL_WORDS, 0));
     // rounds shorter than the host's queueing of the next one (small systems: a round is its ~9 launches) would
     // leave the GPU idle under this pacing, so when the rounds come faster than every 150 us one round stays queued
     // ahead (lag 1), as with the polls below
@@ -141,9 +135,9 @@ static int solve_fair_rounds(lmmhip_ctx* c, double prec) {
     auto t_last = std::chrono::steady_clock::now();
     for (;;) {
       for (int ph = 0; ph < 3; ph++)
-        if (int rc = fb_phase(c, ph))
+        if (int rc = fb_phase(c, d, ph))
           return rc;
-      const int32_t want = int32_t(c->fb_round) - lag;  // rounds started, counting the one just queued
+      const int32_t want = int32_t(c->fair.round) - lag;  // rounds started, counting the one just queued
       for (unsigned spin = 0;; spin++) {
         if (hp[1] || hp[0] >= want) {
           const auto t = std::chrono::steady_clock::now();
@@ -164,7 +158,7 @@ static int solve_fair_rounds(lmmhip_ctx* c, double prec) {
       }
       if (hp[1])
         break;
-      if (c->fb_round > max_rounds)
+      if (c->fair.round > max_rounds)
         return fail(LMMHIP_E_NOCONVERGE, "fair-bottleneck round guard tripped");
     }
     return poll_ctl(c);
@@ -174,14 +168,14 @@ static int solve_fair_rounds(lmmhip_ctx* c, double prec) {
     return rc;
   for (;;) {
     for (int ph = 0; ph < 3; ph++)
-      if (int rc = fb_phase(c, ph))
+      if (int rc = fb_phase(c, d, ph))
         return rc;
     const int32_t* h = nullptr;
-    if (int rc = poll.step(c->d, c->fb_round, false, &h))
+    if (int rc = poll.step(d, c->fair.round, false, &h))
       return rc;
     if (h && h[CTL_DONE])
       break;
-    if (c->fb_round > max_rounds)
+    if (c->fair.round > max_rounds)
       return fail(LMMHIP_E_NOCONVERGE, "fair-bottleneck round guard tripped");
   }
   return poll_ctl(c);  // (the queued round has run: final words for the stats)
@@ -189,30 +183,29 @@ static int solve_fair_rounds(lmmhip_ctx* c, double prec) {
 
 int solve_fair(lmmhip_ctx* c, double prec) {
   c->ran_engine = LMMHIP_RAN_FB_ROUNDS;
-  c->fb_shard = false;
+  FairEngine& e = c->fair;
+  e.shard_xnb = nullptr;
   // shared constraints of at least this many elements get their increments precomputed element-parallel
   // (fbk_acc) and streamed into their chains (fb_chain); shorter ones compute them inside the chain
   // (fb_chain_pull).  Pulling in round 0 and streaming fbk_acc's listed-variable rewrites afterwards measured
   // 3 % slower on C5 (9.68 vs 9.42 ms, same box): the increments' gathers move, they do not go away.
-  c->fb_longmin = uint32_t(std::max(0, env_int("LMMHIP_FB_LONG", 16384)));
-  if (c->fbd_cap < c->d.nnz) {  // increments in CSC order (fbk_acc -> fbk_update_seq)
-    if (int rc = dalloc(c, &c->d.fbd, c->d.nnz))
+  e.longmin = uint32_t(std::max(0, env_int("LMMHIP_FB_LONG", 16384)));
+  if (e.fbd_cap < c->d.nnz) {  // increments in CSC order (fbk_acc -> fbk_update_seq)
+    if (int rc = dalloc(c, &e.f.fbd, c->d.nnz))
       return rc;
-    c->fbd_cap = c->d.nnz;
+    e.fbd_cap = c->d.nnz;
   }
-  if (int rc = scratch(c, c->fair.longl, int64_t(c->d.nC) + 1, &c->d.fb_long))  // the long shared constraints
+  FbDev d{c->d, e.f};  // (the context's own exchange buffers; what follows is this solve's alone)
+  if (int rc = scratch(c, e.longl, int64_t(d.nC) + 1, &d.fb_long))  // the long shared constraints
     return rc;
-  HIPCHK(hipMemsetAsync(c->d.fb_long, 0, sizeof(int32_t), c->stream));
-  hipLaunchKernelGGL(fb_long_list, dim3(grid_for(c->d.nC, kBlock)), dim3(kBlock), 0, c->stream, c->d,
-                     c->fb_longmin);
+  HIPCHK(hipMemsetAsync(d.fb_long, 0, sizeof(int32_t), c->stream));
+  hipLaunchKernelGGL(fb_long_list, dim3(grid_for(d.nC, kBlock)), dim3(kBlock), 0, c->stream, d, e.longmin);
   HIPCHK(hipGetLastError());
   // the long chains by LMMHIP_FB_LONGWG workgroups
-  c->fb_nlb = std::max(1, env_int("LMMHIP_FB_LONGWG", kLongBlocks));
-  c->d.xnb = c->xnb_own;
-  c->d.xmin = c->xmin_own;
-  if (int rc = fb_perm(c))
+  e.nlb = std::max(1, env_int("LMMHIP_FB_LONGWG", kLongBlocks));
+  if (int rc = fb_perm(c, d))
     return rc;
-  return solve_fair_rounds(c, prec);
+  return solve_fair_rounds(c, d, prec);
 }
 
 // ---- block-diagonal batches: one workgroup per system, the system in LDS (lmm_fb_batch_kernels.hpp) ----
@@ -228,7 +221,7 @@ bool fb_batch_fits(const lmmhip_ctx* c) {
 
 int solve_fair_batch(lmmhip_ctx* c, double prec) {
   c->ran_engine = LMMHIP_RAN_FB_BATCH;
-  c->fb_shard = false;
+  c->fair.shard_xnb = nullptr;
   size_t lds = fb_batch_lds_bytes(c->bt_max_nv, c->bt_max_nc, c->bt_max_nnz);
   // both copies of the weights in LDS too when the budget allows (LMMHIP_FB_BATCH_WLDS=0: never; measurement)
   const bool wl = lds + fb_batch_lds_weights(c->bt_max_nnz) <= kBatchLdsMax && env_int("LMMHIP_FB_BATCH_WLDS", 1);
@@ -252,7 +245,7 @@ int solve_fair_batch(lmmhip_ctx* c, double prec) {
   // the chunked engine's budget for this input (solve_fair_rounds): the union's sizes
   const int64_t budget = 64 * (int64_t(c->d.nV) + int64_t(c->d.nC)) + 4096;
   const int max_rounds = int(std::min<int64_t>(budget, INT32_MAX - 1));
-  Dev d = c->d;
+  const FbDev d{c->d, c->fair.f};
   if (wl)
     hipLaunchKernelGGL(fbk_batch_lds<true>, dim3(unsigned(grid)), dim3(kFBB), lds, c->stream, d, c->bt_voff.p,
                        c->bt_coff.p, c->bt_n, prec, c->bt_max_nv, c->bt_max_nc, c->bt_max_nnz, max_rounds,
@@ -309,8 +302,8 @@ int lmmhip_fb_shard_owner(lmmhip_ctx* c, int64_t n_own, const int32_t* own_cnst,
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipStreamSynchronize(c->stream));
   free_owner(c);
-  FbOwner& o = c->fbo;
-  auto get = [&](auto** p, int64_t n, const auto* src) { return c->fbo_allocs.alloc(p, n, src, c->stream); };
+  FbOwner& o = c->fair.owner;
+  auto get = [&](auto** p, int64_t n, const auto* src) { return c->fair.owner_allocs.alloc(p, n, src, c->stream); };
   int32_t *oc, *ov, *cho, *cp;
   uint32_t *opp, *chb;
   double* ow;
@@ -337,19 +330,28 @@ int lmmhip_fb_shard_owner(lmmhip_ctx* c, int64_t n_own, const int32_t* own_cnst,
   o.och_o = cho;
   o.och_b = chb;
   o.cpos = cp;
-  c->fbo_ready = true;
-  c->fbo_nmu = n_mu;
+  c->fair.owner_ready = true;
+  c->fair.owner_nmu = n_mu;
   return 0;
+}
+
+// The view a sharded call launches with: the caller's all-reduced counts for the context's own, and what only
+// solve_fair sets (the locality order, the long-constraint list, the progress words) null — the shard kernels gather
+// mu by variable id.
+static FbDev shard_view(const lmmhip_ctx* c) {
+  FbDev d{c->d, c->fair.f};
+  d.xnb = c->fair.shard_xnb;
+  return d;
 }
 
 int lmmhip_fb_shard_begin(lmmhip_ctx* c, double precision, int32_t* xnb, double* xmu, int64_t mu_off, double* xrem) {
   if (!c || !c->uploaded)
     return fail(LMMHIP_E_STATE, "no system uploaded");
-  if (!c->fbo_ready)
+  if (!c->fair.owner_ready)
     return fail(LMMHIP_E_STATE, "lmmhip_fb_shard_owner first");
   if (!xnb || !xmu || !xrem)
     return fail(LMMHIP_E_ARG, "null exchange buffer");
-  if (mu_off < 0 || mu_off + c->d.nV > c->fbo_nmu)
+  if (mu_off < 0 || mu_off + c->d.nV > c->fair.owner_nmu)
     return fail(LMMHIP_E_ARG, "this shard's mu block lies outside the gathered mu");
   HIPCHK(hipSetDevice(c->device));
   c->pool_used = 0;
@@ -357,33 +359,30 @@ int lmmhip_fb_shard_begin(lmmhip_ctx* c, double precision, int32_t* xnb, double*
   c->launch_round.clear();
   c->launch_ms.clear();
   HIPCHK(hipMemsetAsync(c->d.ctl, 0, CTL_ALLOC * sizeof(int32_t), c->stream));
-  c->d.xnb = xnb;
-  c->d.xmin = c->xmin_own;
-  c->fbo.xmu = xmu;
-  c->fbo.xrem = xrem;
-  c->fbo.mu_off = mu_off;
-  c->fb_shard = true;
-  c->d.mu_p = nullptr;  // (the shard kernels gather mu by variable id; fb_perm is the one-context path's)
+  c->fair.shard_xnb = xnb;
+  c->fair.owner.xmu = xmu;
+  c->fair.owner.xrem = xrem;
+  c->fair.owner.mu_off = mu_off;
   c->last_kind = LMMHIP_KIND_FAIR_BOTTLENECK;
-  return fb_begin(c, precision);
+  return fb_begin(c, shard_view(c), precision);
 }
 
 int lmmhip_fb_shard_step(lmmhip_ctx* c, int phase) {
-  if (!c || !c->fb_shard)
+  if (!c || !c->fair.shard_xnb)
     return fail(LMMHIP_E_STATE, "lmmhip_fb_shard_begin first");
   HIPCHK(hipSetDevice(c->device));
-  return fb_phase(c, phase);
+  return fb_phase(c, shard_view(c), phase);
 }
 
 int lmmhip_fb_shard_pack_mu(lmmhip_ctx* c, int32_t* pos, double* mu, int32_t* count) {
-  if (!c || !c->fb_shard)
+  if (!c || !c->fair.shard_xnb)
     return fail(LMMHIP_E_STATE, "lmmhip_fb_shard_begin first");
   if (!pos || !mu || !count)
     return fail(LMMHIP_E_ARG, "null buffer");
   HIPCHK(hipSetDevice(c->device));
-  Dev& d = c->d;
-  LAUNCH(3, c->fb_round, fbo_pack_mu, grid_for(d.nV, kBlock), kBlock, d, c->fbo, int(c->fb_round == 0), pos, mu,
-         count);
+  const FbDev d = shard_view(c);
+  LAUNCH(3, c->fair.round, fbo_pack_mu, grid_for(d.nV, kBlock), kBlock, d, c->fair.owner, int(c->fair.round == 0), pos,
+         mu, count);
   return 0;
 }
 
@@ -407,7 +406,7 @@ int lmmhip_fb_work(lmmhip_ctx* c, int64_t* out3) {
 }
 
 int lmmhip_fb_shard_poll(lmmhip_ctx* c, int* done, int64_t* rounds) {
-  if (!c || !c->fb_shard)
+  if (!c || !c->fair.shard_xnb)
     return fail(LMMHIP_E_STATE, "lmmhip_fb_shard_begin first");
   HIPCHK(hipSetDevice(c->device));
   if (int rc = poll_ctl(c))

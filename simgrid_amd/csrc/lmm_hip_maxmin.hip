@@ -4,7 +4,7 @@
 // The round engine and the frontier engine are chains of launches and share their host side: round_plan / frontier_plan
 // build what a solve will launch (mode, kernels, grids, cadences, chunk policy: RoundPlan / FrontierPlan in lmm_ctx.hpp)
 // once per solve and read every environment knob of the two engines; run_chunks owns the chunk / poll / guard loop
-// (policy arithmetic: lmm_chunk.hpp).  Each engine works on its own copy of the context's Dev.
+// (policy arithmetic: lmm_chunk.hpp).  Each engine works on its own copy of the context's Dev (the frontier: an FrDev).
 #include <cstring>
 
 #include <array>
@@ -244,7 +244,7 @@ int solve_maxmin(lmmhip_ctx* c, double prec) {
   uint8_t* cmpbits = nullptr;
   if (int rc = round_buffers(c, d, P, &cmpbits))
     return rc;
-  LAUNCH(0, -1, mm_init_cnsts, P.g_init_c, kBlock, d, prec);
+  LAUNCH(0, -1, mm_init_cnsts, P.g_init_c, kBlock, d, static_cast<uint32_t*>(nullptr), prec);
   LAUNCH(1, -1, mm_init_vars, grid_for(d.nV, kBlock), kBlock, d, int(P.mode.rec16()));
   LAUNCH(1, -1, mm_clist, std::min(P.g_c, 2 * c->n_cu), kBlock, d, 1);
   HIPCHK(hipMemsetAsync(d.chgbits, 0, sizeof(uint64_t) * ((d.nC + 127) / 128 * 2 + 2), c->stream));
@@ -355,7 +355,7 @@ static FrontierPlan frontier_plan(const lmmhip_ctx* c, const Dev& d) {
 // control-word copy; 0 / 1 init.
 int solve_maxmin_frontier(lmmhip_ctx* c, double prec) {
   c->ran_engine = LMMHIP_RAN_FRONTIER;
-  Dev d = c->d;  // (a copy: the frontier's buffers stay out of the context's Dev, which the other engines use)
+  FrDev d{c->d, FrFields{}};  // (the engine's view of the system: its buffers are in no other engine's)
   if (!c->vote_diag)  // per-round diagnostic counters only on request (LMMHIP_VOTE_DIAG): they cost atomics
     d.vstat = nullptr;
   const int64_t nnz = std::max<int64_t>(d.nnz, 1);
@@ -385,7 +385,7 @@ int solve_maxmin_frontier(lmmhip_ctx* c, double prec) {
     c->frontier.map_ok = true;
   }
   const FrontierPlan P = frontier_plan(c, d);
-  LAUNCH(0, -1, mm_init_cnsts, grid_for(d.nC, kBlock / kWave), kBlock, d, prec);
+  LAUNCH(0, -1, mm_init_cnsts, grid_for(d.nC, kBlock / kWave), kBlock, d, d.key32, prec);
   LAUNCH(1, -1, fr_init_vars, grid_for(std::max<int64_t>(std::max<int64_t>(d.nV, d.nC), d.nnz / 4), kBlock), kBlock, d);
   auto round_launches = [&](int64_t r) -> int {
     if (r == 0) {

@@ -36,8 +36,10 @@ namespace lmmdev {
 // Waves `wave`, `wave + nwaves`, ... of the grid; returns (on lane 0) the constraints made alive.
 // One group of kInitG lanes per constraint (kWave / kInitG constraints per wave at a time: a wave used to take its
 // ~120 constraints of C2 one after the other, each a dependent chain of loads — 377 us per solve).
+// key32: the frontier engine's 32-bit keys (FrFields::key32), written beside the 16-bit ones; null for the others.
 constexpr int kInitG = 16;
-__device__ __forceinline__ int init_cnsts_waves(const Dev& s, double prec, int64_t wave, int64_t nwaves) {
+__device__ __forceinline__ int init_cnsts_waves(const Dev& s, uint32_t* key32, double prec, int64_t wave,
+                                                int64_t nwaves) {
   const int lane = threadIdx.x & (kWave - 1), gl = lane & (kInitG - 1);
   constexpr int kGpw = kWave / kInitG;
   int alive_cnt = 0;
@@ -82,8 +84,8 @@ __device__ __forceinline__ int init_cnsts_waves(const Dev& s, double prec, int64
       s.nvote[c] = int32_t(e - b);  // no element votes yet
       s.chg[c] = uint16_t(0xFFFF);
       s.key[c] = alive ? ratio_key(r) : uint16_t(kDeadKey);
-      if (s.key32)  // (frontier engine)
-        s.key32[c] = alive ? ratio_key32(r) : kDead32;
+      if (key32)
+        key32[c] = alive ? ratio_key32(r) : kDead32;
       alive_cnt += alive;
     }
   }
@@ -93,9 +95,9 @@ __device__ __forceinline__ int init_cnsts_waves(const Dev& s, double prec, int64
 // (Round 6: the per-wave count of alive constraints this kernel used to add into one control word — read by nobody —
 // was 8,192 atomics on one address per solve, serialised in the memory-side unit after the grid's short work: the
 // whole 74-us init of C4 and ~70 us of C2's.)
-__global__ void __launch_bounds__(kBlock) mm_init_cnsts(Dev s, double prec) {
+__global__ void __launch_bounds__(kBlock) mm_init_cnsts(Dev s, uint32_t* key32, double prec) {
   const int64_t wave = (int64_t(blockIdx.x) * kBlock + threadIdx.x) / kWave;
-  init_cnsts_waves(s, prec, wave, int64_t(gridDim.x) * (kBlock / kWave));
+  init_cnsts_waves(s, key32, prec, wave, int64_t(gridDim.x) * (kBlock / kWave));
 }
 
 // F: also the packed row records of buffer 0 in that form (the multi-launch engine's init only; Rec8: where the solve

@@ -342,7 +342,7 @@ __global__ void __launch_bounds__(kPB) mm_persist(Dev s, unsigned* barw, double 
   if (!bar_rdv(b, rdv_ticks, hflag))
     return;
   unsigned gen = 0;
-  init_cnsts_waves(s, prec, pwave(), int64_t(gridDim.x) * kPW);  // init (maxmin.cpp:509-555)
+  init_cnsts_waves(s, nullptr, prec, pwave(), int64_t(gridDim.x) * kPW);  // init (maxmin.cpp:509-555)
   init_vars_range<RowForm::Arrays>(s, int64_t(blockIdx.x) * kPB + threadIdx.x, int64_t(gridDim.x) * kPB);
   if (!grid_sync(b, ++gen))
     return;
