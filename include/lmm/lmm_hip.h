@@ -180,6 +180,33 @@ int lmmhip_get_usage(lmmhip_ctx* ctx, double* usage_out);
  * context-owned buffer without synchronising the host; work queued on that stream afterwards sees the usages.
  * Valid until the next upload, flatten, solve or usage call on the context. */
 int lmmhip_usage_device_ptr(lmmhip_ctx* ctx, const double** dptr);
+/* Max-min certificate of the solved system, computed on the device from what HBM holds (no value leaves it):
+ *   a constraint is judged when bound > bound * precision (maxmin.cpp:524); with U_c as lmmhip_get_usage gives it, a
+ *   judged one is infeasible when U_c - bound > bound * precision, saturated when NOT (bound - U_c > bound *
+ *   precision), and its excess is (U_c - bound) / bound;
+ *   a variable is judged when penalty > 0 and value > 0; it is at its bound when bound > 0 and |value - bound| <=
+ *   max(precision, 1e-9 * bound); otherwise its witness is the first constraint in its CSR row order that is judged
+ *   and saturated and on which its level value * penalty reaches the largest level of the constraint's elements
+ *   (level >= top * (1 - 1e-9)); a judged variable with neither is unbottlenecked.
+ * The solution is a max-min fair point iff n_infeasible == 0 and n_unbottlenecked == 0.  witness (n_var int32, dense
+ * order, or NULL) gets each variable's witness: the dense constraint index, or a LMMHIP_WIT_* code.
+ * Valid after a successful solve of either kind by any engine, until the next upload, flatten or solve.  The call
+ * reads the values, penalties, bounds and structure as they are in HBM when it runs: lmmhip_update_vars and
+ * lmmhip_update_cnsts do not end the solved state, so after them the certificate judges the old values against
+ * the new penalties and bounds.  LMMHIP_KIND_FAIR_BOTTLENECK, whose fixed point is not the max-min condition, gets
+ * the constraint half only: n_unbottlenecked = -1, n_judged_var = n_at_bound = 0, every witness
+ * LMMHIP_WIT_NOT_JUDGED.  Counts are integer sums and max_excess a maximum, folded in a fixed order: two calls give
+ * the same bytes.  Runs on the context's current stream and synchronises it.  Errors as lmmhip_get_usage:
+ * LMMHIP_E_STATE without a solved system (a NULL context included), LMMHIP_E_ARG for a NULL out. */
+typedef struct lmmhip_cert {
+  double max_excess;                 /* largest excess over the judged constraints; -1e300 when none is judged */
+  int64_t n_infeasible, n_unbottlenecked;
+  int64_t n_judged_cnst, n_judged_var, n_at_bound;
+} lmmhip_cert;
+#define LMMHIP_WIT_AT_BOUND (-1)
+#define LMMHIP_WIT_NONE (-2)
+#define LMMHIP_WIT_NOT_JUDGED (-3)
+int lmmhip_certificate(lmmhip_ctx* ctx, double precision, lmmhip_cert* out, int32_t* witness);
 /* Variables the last flatten put in the system — the Lazy models' modified_set_ side effect of the
  * solve (every variable of an active element of a listed constraint, maxmin.cpp:536-538) — in the
  * caller's id space: dense CSR indices after lmmhip_upload, host variable slots after

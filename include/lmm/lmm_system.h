@@ -147,6 +147,22 @@ int lmm_flat_export_cnsts(lmm_sys* s, int64_t* cnst_ids, int64_t cap);
  * being solved again, so the answer always describes the last solve only.  lmm_constraint_get_usage (the host
  * walk over the fetched values) is unchanged. */
 int64_t lmm_device_usage(lmm_sys* s, int64_t* cnst_ids, double* usage, int64_t cap);
+/* Max-min certificate of the last device solve, computed on the device over the flattened system from the values in
+ * HBM (lmmhip_certificate, include/lmm/lmm_hip.h, states the rules): the three numbers lmm_check_certificate gives
+ * after lmm_fetch, with no lmm_fetch — max_excess up to the order of the usage sums.  FairBottleneck systems get the
+ * feasibility half, *n_unbottlenecked = -1.  Returns -1 with lmm_last_error() before any device solve of the system
+ * (or after lmm_solve_batch), as lmm_device_usage; like it, in selective mode it describes the last solve's
+ * flattened system only: constraints and variables outside the solve list are not judged. */
+int lmm_device_certificate(lmm_sys* s, double precision, double* max_excess, int64_t* n_infeasible,
+                           int64_t* n_unbottlenecked);
+/* The witnesses behind that certificate, at the configured precision (lmm_get_precision): every variable of the
+ * flattened system in dense order, var_ids[d] with cnst_ids[d] = the constraint that bottlenecks it — the first one in
+ * the variable's element order that is saturated and on which the variable's level value * penalty is the largest —
+ * or a negative code as it is: LMMHIP_WIT_AT_BOUND (-1, the variable sits at its own bound), LMMHIP_WIT_NONE (-2,
+ * unbottlenecked), LMMHIP_WIT_NOT_JUDGED (-3: value or penalty not positive, or a FairBottleneck system).  Returns the
+ * count n (cap >= n); null arrays = size query; -1 with lmm_last_error() as lmm_device_certificate.  No lmm_fetch
+ * needed; resident mode or not. */
+int64_t lmm_device_bottlenecks(lmm_sys* s, int64_t* var_ids, int64_t* cnst_ids, int64_t cap);
 /* Solve n independent systems as one device launch sequence (disjoint union). */
 int lmm_solve_batch(lmm_sys** systems, int n);
 

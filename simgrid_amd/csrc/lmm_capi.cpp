@@ -414,6 +414,20 @@ int64_t lmm_device_usage(lmm_sys* s, int64_t* cnst_ids, double* usage, int64_t c
   }
 }
 
+int lmm_device_certificate(lmm_sys* s, double prec, double* max_excess, int64_t* n_infeasible,
+                           int64_t* n_unbottlenecked) {
+  GUARD(s->sys.device_certificate(prec, max_excess, n_infeasible, n_unbottlenecked))
+}
+
+int64_t lmm_device_bottlenecks(lmm_sys* s, int64_t* var_ids, int64_t* cnst_ids, int64_t cap) {
+  try {
+    return s->sys.device_bottlenecks(var_ids, cnst_ids, cap);
+  } catch (const std::exception& ex) {
+    g_err = ex.what();
+    return -1;
+  }
+}
+
 int lmm_solve_batch(lmm_sys** systems, int n) {
   try {
     std::vector<System*> v(size_t(n > 0 ? n : 0));

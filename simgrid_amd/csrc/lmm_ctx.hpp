@@ -333,6 +333,7 @@ struct lmmhip_ctx {
   int res_flat_kind = LMMHIP_KIND_MAXMIN;  // solver the last resident flatten built for
   Scr sat_out, tv_out;  // lmmhip_get_saturated / lmmhip_get_touched_vars staging
   Scr usage_out, tc_out;  // lmmhip_get_usage and lmmhip_usage_device_ptr / lmmhip_get_touched_cnsts
+  Scr cert_top, cert_wit, cert_part;      // lmmhip_certificate: sattop, witness, the workgroups' parts + the result
   Scr cc_par, cc_flag, cc_rank, cc_out;  // lmmhip_components
   RoundEngine rounds;
   FrontierEngine frontier;

@@ -881,6 +881,44 @@ int lmmhip_usage_device_ptr(lmmhip_ctx* c, const double** dptr) {
   return 0;
 }
 
+int lmmhip_certificate(lmmhip_ctx* c, double precision, lmmhip_cert* out, int32_t* witness) {
+  if (!c || !c->uploaded || !c->solved)
+    return fail(LMMHIP_E_STATE, "no solved system");
+  if (!out)
+    return fail(LMMHIP_E_ARG, "null output");
+  HIPCHK(hipSetDevice(c->device));
+  const Dev& d = c->d;
+  const bool fair = c->last_kind == LMMHIP_KIND_FAIR_BOTTLENECK;
+  const int gc = grid_for(d.nC, kBlock / kWave), gv = fair ? 0 : grid_for(d.nV, kBlock);
+  double* top = nullptr;
+  int32_t* wit = nullptr;
+  lmmhip_cert* part = nullptr;  // [gc + gv] the workgroups' parts, then the result
+  if (int rc = scratch(c, c->cert_top, d.nC, &top))
+    return rc;
+  if (int rc = scratch(c, c->cert_part, int64_t(gc) + gv + 1, &part))
+    return rc;
+  if (witness && !fair)
+    if (int rc = scratch(c, c->cert_wit, d.nV, &wit))
+      return rc;
+  hipLaunchKernelGGL(cert_cnst, dim3(gc), dim3(kBlock), 0, c->stream, d, precision, top, part);
+  HIPCHK(hipGetLastError());
+  if (!fair) {
+    hipLaunchKernelGGL(cert_var, dim3(gv), dim3(kBlock), 0, c->stream, d, precision, static_cast<const double*>(top),
+                       wit, part + gc);
+    HIPCHK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(cert_fold, dim3(1), dim3(kBlock), 0, c->stream, static_cast<const lmmhip_cert*>(part), gc, gv,
+                     part + gc + gv);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, part + gc + gv, sizeof(lmmhip_cert), hipMemcpyDeviceToHost, c->stream));
+  if (wit && d.nV)
+    HIPCHK(hipMemcpyAsync(witness, wit, sizeof(int32_t) * size_t(d.nV), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (witness && fair)
+    std::fill(witness, witness + d.nV, int32_t(LMMHIP_WIT_NOT_JUDGED));
+  return 0;
+}
+
 int lmmhip_components(lmmhip_ctx* c, int32_t* var_label, int32_t* cnst_label, int64_t* ncomp) {
   if (!c || !c->uploaded)
     return fail(LMMHIP_E_STATE, "no system uploaded");

@@ -22,6 +22,7 @@
 #include <stdexcept>
 
 #include "../../include/lmm/lmm_hip.h"
+#include "lmm_cert.hpp"
 
 namespace simgrid_amd {
 namespace lmm {
@@ -651,31 +652,29 @@ void System::check_certificate(double prec, double* max_excess, int64_t* n_infea
       top[c] = std::max(top[c], values_[x.var] * r.penalty);
     }
   }
-  double worst = -1e300;
+  double worst = lmmcert::kNoExcess;
   int64_t infeasible = 0, unb = 0;
   std::vector<uint8_t> sat(cnsts_.size(), 0);
   for (size_t c = 0; c < cnsts_.size(); c++) {
     const double b = cnsts_[c].bound;
-    if (!(b > b * prec))  // ignored by lmm_solve (maxmin.cpp:524)
+    if (!lmmcert::judged(b, prec))  // ignored by lmm_solve (maxmin.cpp:524)
       continue;
-    const double ex = (usage[c] - b) / b;
-    worst = std::max(worst, ex);
-    if (usage[c] - b > b * prec)
-      infeasible++;
-    sat[c] = !(b - usage[c] > b * prec);
+    worst = std::max(worst, lmmcert::excess(usage[c], b));
+    infeasible += lmmcert::infeasible(usage[c], b, prec);
+    sat[c] = lmmcert::saturated(usage[c], b, prec);
   }
   for (Id v = 0; v < Id(vars_.size()); v++) {
     const VarRec& r = vars_[v];
     const double rv = values_[v];
     if (!r.live || !(r.penalty > 0) || !(rv > 0))
       continue;
-    if (r.bound > 0 && std::fabs(rv - r.bound) <= std::max(prec, 1e-9 * r.bound))
-      continue;  // at its bound
+    if (lmmcert::at_bound(rv, r.bound, prec))
+      continue;
     const double lvl = rv * r.penalty;
     bool ok = false;
     for (int i = 0; i < r.n_elems && !ok; i++) {
       const ElemRec& x = elems_[r.ebase + i];
-      ok = x.weight > 0 && sat[x.cnst] && lvl >= top[x.cnst] * (1 - 1e-9);
+      ok = x.weight > 0 && sat[x.cnst] && lmmcert::carries(lvl, top[x.cnst]);
     }
     unb += !ok;
   }
@@ -913,6 +912,45 @@ int64_t System::device_usage(int64_t* ids, double* usage, int64_t cap) {
   }
   if (lmmhip_get_usage(ctx(), usage))
     fatal(std::string("device usage failed: ") + lmmhip_last_error());
+  return n;
+}
+
+void System::device_certificate(double prec, double* max_excess, int64_t* n_infeasible, int64_t* n_unbottlenecked) {
+  check(dev_solved_, "device_certificate: no device solve of this system to certify");
+  lmmhip_cert cert{};
+  if (lmmhip_certificate(ctx(), prec, &cert, nullptr))
+    fatal(std::string("device certificate failed: ") + lmmhip_last_error());
+  *max_excess = cert.max_excess;
+  *n_infeasible = cert.n_infeasible;
+  *n_unbottlenecked = cert.n_unbottlenecked;
+}
+
+int64_t System::device_bottlenecks(int64_t* var_ids, int64_t* cnst_ids, int64_t cap) {
+  check(dev_solved_, "device_bottlenecks: no device solve of this system to read witnesses from");
+  int64_t n = int64_t(flat_.dense_vars.size()), nc = int64_t(flat_.dense_cnsts.size());
+  if (dev_resident_ &&
+      (lmmhip_get_touched_vars(ctx(), nullptr, 0, &n) || lmmhip_get_touched_cnsts(ctx(), nullptr, 0, &nc)))
+    fatal(std::string("device bottlenecks failed: ") + lmmhip_last_error());
+  if (!var_ids && !cnst_ids)
+    return n;
+  check(var_ids && cnst_ids && cap >= n, "device_bottlenecks: arrays smaller than the solved system's variable count");
+  // the dense-to-id maps of device_usage and the touched-variable path
+  std::vector<int64_t> cid(flat_.dense_cnsts.begin(), flat_.dense_cnsts.end());
+  if (dev_resident_) {
+    std::vector<int32_t> rv(static_cast<size_t>(n)), rc(static_cast<size_t>(nc));
+    if (lmmhip_get_touched_vars(ctx(), rv.data(), n, &n) || lmmhip_get_touched_cnsts(ctx(), rc.data(), nc, &nc))
+      fatal(std::string("device bottlenecks failed: ") + lmmhip_last_error());
+    std::copy(rv.begin(), rv.end(), var_ids);
+    cid.assign(rc.begin(), rc.end());
+  } else {
+    std::copy(flat_.dense_vars.begin(), flat_.dense_vars.end(), var_ids);
+  }
+  std::vector<int32_t> wit(static_cast<size_t>(n));
+  lmmhip_cert cert{};
+  if (lmmhip_certificate(ctx(), maxmin_precision, &cert, wit.data()))
+    fatal(std::string("device bottlenecks failed: ") + lmmhip_last_error());
+  for (int64_t d = 0; d < n; d++)
+    cnst_ids[d] = wit[size_t(d)] < 0 ? int64_t(wit[size_t(d)]) : cid[size_t(wit[size_t(d)])];
   return n;
 }
 

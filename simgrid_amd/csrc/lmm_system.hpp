@@ -118,6 +118,14 @@ public:
   // Nothing is kept per constraint slot between solves (a constraint can leave every list without being solved
   // again, so a kept table would go stale).
   int64_t device_usage(int64_t* ids, double* usage, int64_t cap);
+  // Max-min certificate of the last device solve, computed on the device over the flattened system
+  // (lmmhip_certificate, the rules of lmm_cert.hpp): what check_certificate returns after a fetch(), with no fetch.
+  // Like device_usage it describes the last solve's flattened system only, and throws before any device solve.
+  void device_certificate(double prec, double* max_excess, int64_t* n_infeasible, int64_t* n_unbottlenecked);
+  // ... and its witnesses: every variable of the flattened system in dense order, var_ids[d] with cnst_ids[d] = the
+  // id of the constraint that bottlenecks it, or a negative LMMHIP_WIT_* code.  Returns the count; null arrays = size
+  // query.
+  int64_t device_bottlenecks(int64_t* var_ids, int64_t* cnst_ids, int64_t cap);
 
   // read API (maxmin.hpp:296-331, :188-247)
   double get_value(Id v) const { return values_[v]; }

@@ -50,6 +50,29 @@ class LmmhipStats(ct.Structure):
                 ("kernel_ms", D * 8), ("kernel_launches", I64 * 8)]
 
 
+class LmmhipCert(ct.Structure):
+    """lmmhip_cert (include/lmm/lmm_hip.h)."""
+    _fields_ = [("max_excess", D), ("n_infeasible", I64), ("n_unbottlenecked", I64), ("n_judged_cnst", I64),
+                ("n_judged_var", I64), ("n_at_bound", I64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# witness codes of lmmhip_certificate / lmm_device_bottlenecks (LMMHIP_WIT_*)
+WIT_AT_BOUND, WIT_NONE, WIT_NOT_JUDGED = -1, -2, -3
+
+
+def ctx_certificate(ctx, n_var, precision, witness=True):
+    """lmmhip_certificate on a device context holding a solved system of n_var variables: (the struct as a dict, the
+    dense int32 witness array or None)."""
+    cert = LmmhipCert()
+    wit = np.empty(n_var, np.int32) if witness else None
+    _check_hip(lib().lmmhip_certificate(ctx, precision, ct.byref(cert),
+                                        wit.ctypes.data_as(ct.POINTER(ct.c_int32)) if witness else None))
+    return cert.as_dict(), wit
+
+
 SIGNATURES = {
     # include/lmm/lmm_system.h
     "lmm_set_precision": (None, [D]),
@@ -112,6 +135,8 @@ SIGNATURES = {
     "lmm_flat_export_order": (I, [P, I64, PI64]),
     "lmm_flat_export_cnsts": (I, [P, PI64, I64]),
     "lmm_device_usage": (I64, [P, PI64, PD, I64]),
+    "lmm_device_certificate": (I, [P, D, PD, PI64, PI64]),
+    "lmm_device_bottlenecks": (I64, [P, PI64, PI64, I64]),
     "lmm_solve_batch": (I, [ct.POINTER(P), I]),
     "lmm_system_device_ctx": (P, [P]),
     "lmm_check_certificate": (I, [P, D, PD, PI64, PI64]),
@@ -154,6 +179,7 @@ SIGNATURES = {
     "lmmhip_get_usage": (I, [P, PD]),
     "lmmhip_usage_device_ptr": (I, [P, ct.POINTER(P)]),
     "lmmhip_get_touched_cnsts": (I, [P, ct.POINTER(ct.c_int32), I64, PI64]),
+    "lmmhip_certificate": (I, [P, D, ct.POINTER(LmmhipCert), ct.POINTER(ct.c_int32)]),
     "lmmhip_get_stats": (I, [P, P]),
     "lmmhip_set_profiling": (I, [P, I]),
     "lmmhip_launch_profile": (I, [P, PI, PI, ct.POINTER(ct.c_float), I]),
@@ -592,6 +618,33 @@ class System:
         if lib().lmm_device_usage(self.h, ids.ctypes.data_as(PI64), u.ctypes.data_as(PD), n) != n:
             raise LmmError(lib().lmm_last_error().decode())
         return ids, u
+
+    def device_certificate(self, precision=None):
+        """check_certificate() of the last device solve, computed on the device with no fetch()
+        (lmm_device_certificate): (max relative excess, #infeasible constraints, #variables without a bottleneck) of
+        the solved (flattened) system.  FairBottleneck: the feasibility half, #unbottlenecked = -1."""
+        ex, ni, nu = D(), I64(), I64()
+        p = get_precision() if precision is None else precision
+        _check(lib().lmm_device_certificate(self.h, p, ct.byref(ex), ct.byref(ni), ct.byref(nu)))
+        return ex.value, ni.value, nu.value
+
+    def device_certificate_dense(self, precision=None):
+        """The whole lmmhip_cert of this system's device context as a dict, and the dense witness array (int32: per
+        dense variable the dense constraint that bottlenecks it, or WIT_AT_BOUND / WIT_NONE / WIT_NOT_JUDGED)."""
+        p = get_precision() if precision is None else precision
+        return ctx_certificate(self.device_ctx(), self.last_stats()["n_var"], p)
+
+    def device_bottlenecks(self):
+        """(variable ids, constraint ids) of the last device solve (lmm_device_bottlenecks): every variable of the
+        solved system in dense order with the constraint that bottlenecks it, or a negative WIT_* code.  Needs no
+        fetch()."""
+        n = lib().lmm_device_bottlenecks(self.h, None, None, 0)
+        if n < 0:
+            raise LmmError(lib().lmm_last_error().decode())
+        vs, cs = np.empty(n, np.int64), np.empty(n, np.int64)
+        if lib().lmm_device_bottlenecks(self.h, vs.ctypes.data_as(PI64), cs.ctypes.data_as(PI64), n) != n:
+            raise LmmError(lib().lmm_last_error().decode())
+        return vs, cs
 
     def flat_cnst_ids(self):
         """Constraint id of every dense constraint of the system multi.export_flat(self) describes

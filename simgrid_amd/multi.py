@@ -321,6 +321,12 @@ class DeviceBatch:
         self._check(self.L.lmmhip_get_usage(self.ctx, out.ctypes.data_as(ct.POINTER(ct.c_double))))
         return out
 
+    def certificate(self, precision=None):
+        """The max-min certificate of the last solve over the union of the systems (lmmhip_certificate): (the
+        lmmhip_cert as a dict, the witness per dense variable of the concatenated systems, as dense constraint
+        indices of the concatenation).  FairBottleneck batches get the feasibility half."""
+        return lmm.ctx_certificate(self.ctx, self.n_var, self.prec if precision is None else precision)
+
     def flat(self):
         """The concatenated flattened system as a Flat (dense ids; var_ids / csc_order unset)."""
         vp, ci, w, pen, vb, cb, cf = self.arrays
