@@ -279,6 +279,13 @@ int lmmhip_ctx_set_engine(lmmhip_ctx* ctx, int engine);
  * engine directly.  Persistent launches of one process are serialised per device, so two Systems never starve
  * each other. */
 int lmmhip_engine_fallbacks(lmmhip_ctx* ctx, int64_t* n);
+/* The key window of the context's last solve, which the round engine ran (else LMMHIP_E_STATE): out[0] = base (the f32
+ * bits of the window's lower end), out[1] = shift; the 16-bit keys of that solve were the codes
+ * min(0xFFFD, (max(bits(f32_rd(ratio)), base) - base) >> shift), with the window chosen on the device from the solve's
+ * initial ratios (LMMHIP_KEY_WINDOW=0: base 0, shift 16).  After a solve under lmmhip_set_profiling with
+ * LMMHIP_VOTE_DIAG=1: out[2] = the keys the updates stored over the solve, out[3] = those of them at the window's top
+ * code; else both 0. */
+int lmmhip_key_window(lmmhip_ctx* ctx, int64_t* out);
 /* The engine that ran the last successful lmmhip_solve of this context (LMMHIP_E_STATE before any): the
  * max-min persistent / round / frontier engines (a persistent launch that fell back to the round engine reports
  * ROUNDS), the max-min batch engine, FairBottleneck's chunked round engine, or its batch engine. */

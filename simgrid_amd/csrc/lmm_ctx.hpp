@@ -138,6 +138,7 @@ struct FlatBufs {
 struct RoundEngine {
   Scr crec[3], rdq[2], rqst, useg, ucnt;
   Scr cmpbits;  // RowForm::Rec16: the compaction count's alive bits, one per row
+  Scr kwmm;     // the init's per-workgroup extremes of the alive ratios (mm_key_window)
 };
 // What one round-engine solve launches (round_plan: the context, the system's sizes and the environment, read once per
 // solve — tests change the environment between solves); const from there on, handed to everything that launches.
@@ -163,6 +164,10 @@ struct RoundPlan {
   int cap_sat = 0, sat_max = 0;  // saturation: grid cap (0: none), block cap of the uncapped grid
   // cadences: compaction of the alive rows (every cmp_every rounds, rewritten under cmp_pct % alive), constraint list
   int cmp_every = 48, cmp_pct = 75, cl_every = 8;
+  // the 16-bit keys as codes of a window chosen on the device from this solve's initial ratios (LMMHIP_KEY_WINDOW;
+  // false: the legacy window), distinct up to key_headroom times the initial maximum (lmm_keywin.hpp)
+  bool key_window = true;
+  double key_headroom = 4.0;  // (kKeyHeadroom, lmm_hip_maxmin.hip)
   ChunkPolicy chunk;
   int64_t tail_rows = 0, tail_cnst = 0;  // the solve is in its tail at this many alive rows / listed constraints
 };

@@ -8,6 +8,8 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "lmm_keywin.hpp"
+
 namespace lmmdev {
 
 constexpr int kBlock = 256;
@@ -47,6 +49,12 @@ enum : int {
   // slots after the control words (CTL_FBW_AT; round 6: one counter word took one atomic per wave, 8,192 per
   // fb_var_inc launch, ~11 ns each on one address, drained after the grid's last wave)
   CTL_FBW = 24,
+  // round engine: the solve's key window (lmm_keywin.hpp; mm_key_window writes it, every kernel that makes a key reads
+  // it) and, measurement only (mm_key_diag), the keys mm_update stored over the solve and those of them at kKeyTop
+  CTL_KW_BASE = 25,
+  CTL_KW_SHIFT = 26,
+  CTL_KW_STORES = 27,
+  CTL_KW_CLAMP = 28,
   CTL_WORDS = 32
 };
 constexpr int kFbwSlots = 64;
@@ -330,15 +338,13 @@ constexpr int32_t kRetired = -2;   // row target: variable fixed or dropped (ski
 
 __device__ __forceinline__ double dinf() { return __builtin_huge_val(); }
 
-// 16-bit monotone key: round the ratio down to f32, keep the upper 16 bits (sign, exponent, 7 bits
-// of mantissa).  Monotone non-decreasing, so key(a) < key(b) => a < b; equal keys need the exact
-// fp64 comparison.
-#ifndef LMM_KEY_MANT
-#define LMM_KEY_MANT 7  // mantissa bits of the key (build knob, measurement)
-#endif
-__device__ __forceinline__ uint16_t ratio_key(double r) {
-  float f = __double2float_rd(r);
-  return uint16_t(__float_as_uint(f) >> (23 - LMM_KEY_MANT));
+// 16-bit monotone key: the ratio rounded down to f32, its bits as a code of the window w (lmm_keywin.hpp; the legacy
+// window keeps the upper 16 bits: sign, exponent, 7 bits of mantissa).  Monotone non-decreasing, so key(a) < key(b)
+// => a < b; equal keys need the exact fp64 comparison.
+__device__ __forceinline__ uint16_t ratio_key(double r, KeyWin w) { return uint16_t(key_code(r, w)); }
+// The round engine's window of this solve, from the control words (uniform: two scalar loads).
+__device__ __forceinline__ KeyWin key_win_ctl(const int32_t* ctl) {
+  return KeyWin{uint32_t(ctl[CTL_KW_BASE]), ctl[CTL_KW_SHIFT]};
 }
 
 // 32-bit monotone key (frontier engine): the ratio rounded down to f32, its bits.  Ties between different

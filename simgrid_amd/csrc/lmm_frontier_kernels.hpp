@@ -133,12 +133,12 @@ enum : int { FR_STAY = 0, FR_MOVE = 1, FR_BOUND = 2, FR_DROP = 3 };
 
 // The floor of a vote for a constraint of key mk (row_floor with 32-bit keys): min key over the row's other
 // constraints and, bounded, the key of the level bound * penalty; 0 = sensitive (a key-level tie).
-__device__ __forceinline__ uint32_t row_floor32(uint32_t sk, uint32_t mk, double vb, double p) {
-  uint32_t fl = sk;
-  if (vb > 0)
-    fl = min(fl, ratio_key32(vb * p));
+// (kb: the 32-bit key of the level bound * penalty, kDead32 for an unbounded variable: bound_key32)
+__device__ __forceinline__ uint32_t row_floor32(uint32_t sk, uint32_t mk, uint32_t kb) {
+  const uint32_t fl = min(sk, kb);
   return fl <= mk ? 0u : fl;
 }
+__device__ __forceinline__ uint32_t bound_key32(double vb, double p) { return vb > 0 ? ratio_key32(vb * p) : kDead32; }
 
 // (an: the dependent levels: lv[1] row (csr_cs) + bound / penalty, lv[2] keys + floors, lv[3] the rest of the row +
 // exact ratios, lv[4] the vote's stores and atomics issued)
@@ -212,8 +212,12 @@ __device__ __forceinline__ int fr_revote(const FrDev& s, int v, int t, uint32_t 
     if (k == mk)
       newt = min(newt, c);
   }
+  // the key decides unless it ties, for the bound level too (vote_row): kb < mk fixes the variable at its bound with no
+  // ratio load, kb > mk leaves the exact ratios to the ties among the constraints, kb == mk takes the exact compare
+  const uint32_t kb = bound_key32(vb, p);
+  const bool bfix = kb < mk;
   double minr = dinf();
-  if (nmin > 1 || vb > 0) {  // exact ratios at the minimal key: lexicographic min of (ratio, id)
+  if ((nmin > 1 && !bfix) || kb == mk) {  // exact ratios at the minimal key: lexicographic min of (ratio, id)
     newt = INT_MAX;
     double rr[R];  // the tied constraints' ratios, all loads issued before the first compare (one dependent level:
                    // a compare right after each conditional load waited for the loads one at a time)
@@ -238,7 +242,7 @@ __device__ __forceinline__ int fr_revote(const FrDev& s, int v, int t, uint32_t 
     }
   }
   an.level(3, minr + double(newt + nmin));
-  if (vb > 0 && vb * p < minr) {  // fixed at its bound (maxmin.cpp:587-589)
+  if (bfix || (kb == mk && vb * p < minr)) {  // fixed at its bound (maxmin.cpp:587-589)
     s.vstate[v] = round + 1;
     s.x[v] = vb;
     if (t >= 0 && kt != kDead32)
@@ -273,7 +277,7 @@ __device__ __forceinline__ int fr_revote(const FrDev& s, int v, int t, uint32_t 
   }
   // (a floor of kDead32 — no other alive constraint, unbounded — is stored as kDead32 - 1: the vote then
   // moves only when newt itself dies, exactly as before)
-  const uint32_t fl = min(row_floor32(sk, mk, vb, p), kNoVoter - 1u);
+  const uint32_t fl = min(row_floor32(sk, mk, kb), kNoVoter - 1u);
   if (kMinfl && !kEarly)  // (loaded before the slot's store: a load issued after a store waits for it)
     mfn = s.minfl[newt];
   s.vslot[slot] = fl;

@@ -703,6 +703,18 @@ int lmmhip_engine_fallbacks(lmmhip_ctx* c, int64_t* n) {
   return 0;
 }
 
+int lmmhip_key_window(lmmhip_ctx* c, int64_t* out) {
+  if (!c || !out)
+    return fail(LMMHIP_E_ARG, "null argument");
+  if (!c->solved || c->last_engine != LMMHIP_RAN_ROUNDS)
+    return fail(LMMHIP_E_STATE, "the last solve of this context did not run the round engine");
+  out[0] = int64_t(uint32_t(c->h_ctl.p[CTL_KW_BASE]));
+  out[1] = c->h_ctl.p[CTL_KW_SHIFT];
+  out[2] = c->h_ctl.p[CTL_KW_STORES];
+  out[3] = c->h_ctl.p[CTL_KW_CLAMP];
+  return 0;
+}
+
 int lmmhip_ctx_set_engine(lmmhip_ctx* c, int engine) {
   if (!c)
     return fail(LMMHIP_E_ARG, "null context");

@@ -19,6 +19,9 @@
 #include "lmm_frontier_kernels.hpp"
 #include "lmm_batch_kernels.hpp"
 
+// The round engine's key window stays distinct up to this factor above the solve's initial maximum ratio
+// (RoundPlan::key_headroom; DESIGN.md "Key window" has the clamped shares it was chosen from).
+constexpr double kKeyHeadroom = 4.0;
 constexpr int64_t kAutoPersistVars = 1 << 18;   // LMMHIP_ENGINE_AUTO: one of the single-GPU small-system engines up to
 constexpr int64_t kAutoPersistMaxVars = 1 << 14;  // this many variables: persistent up to 2^14, frontier above
 
@@ -165,6 +168,14 @@ static RoundPlan round_plan(const lmmhip_ctx* c, const Dev& d) {
   P.update = kUpdTable[m.upd().index()];
   P.g_init_c = grid_for(d.nC, kBlock / kWave);
   P.g_c = grid_for(d.nC, kBlock);
+  // LMMHIP_KEY_WINDOW=0: the legacy key window {0, 16} (the f32's upper 16 bits) instead of the one mm_key_window
+  // chooses from the solve's initial ratios; results are the same under every window (lmm_keywin.hpp).
+  // LMMHIP_KEY_HEADROOM (measurement knob): the window keeps the codes distinct up to this factor above the initial
+  // maximum ratio (DESIGN.md "Key window": the choice and the clamped share it was read from).
+  P.key_window = env_int("LMMHIP_KEY_WINDOW", 1) != 0;
+  const char* kh = std::getenv("LMMHIP_KEY_HEADROOM");
+  const double khv = kh ? std::atof(kh) : 0.0;
+  P.key_headroom = khv >= 1.0 ? khv : kKeyHeadroom;
   // Compaction cadence (knobs): alive rows are re-counted every cmp_every rounds and rewritten when
   // fewer than cmp_pct % of the scanned rows are alive; the alive-constraint list every cl_every rounds.
   // Both decide and switch buffers on the device (ctl CTL_BUF / CTL_CB): no host round trip.
@@ -201,7 +212,10 @@ static RoundPlan round_plan(const lmmhip_ctx* c, const Dev& d) {
 // The plan's buffers, into the solve's own Dev: the context's never carries them (lmm_dev.hpp), so no other engine —
 // whose compactions do not maintain the row records — ever sees them.
 // (cmpbits: the compaction's alive bits, RowForm::Rec16 only — an argument of its two kernels, not part of the Dev)
-static int round_buffers(lmmhip_ctx* c, Dev& d, const RoundPlan& P, uint8_t** cmpbits) {
+static int round_buffers(lmmhip_ctx* c, Dev& d, const RoundPlan& P, uint8_t** cmpbits, double** kwmm) {
+  if (P.key_window)
+    if (int rc = scratch(c, c->rounds.kwmm, 2 * int64_t(P.g_init_c), kwmm))
+      return rc;
   for (int k = 0; k < 3 && P.mode.rec(); k++)  // (the member of RowRecs the RowForm selects)
     if (int rc = P.mode.rec16() ? scratch(c, c->rounds.crec[k], int64_t(d.nV) + 1, &d.crec[k].r16)
                                 : scratch(c, c->rounds.crec[k], int64_t(d.nV) + 1, &d.crec[k].r8))
@@ -242,10 +256,13 @@ int solve_maxmin(lmmhip_ctx* c, double prec) {
   Dev d = c->d;  // (a copy, as in the other engines: the mode's buffers go into it alone)
   const RoundPlan P = round_plan(c, d);
   uint8_t* cmpbits = nullptr;
-  if (int rc = round_buffers(c, d, P, &cmpbits))
+  double* kwmm = nullptr;  // (null: the legacy key window)
+  if (int rc = round_buffers(c, d, P, &cmpbits, &kwmm))
     return rc;
-  LAUNCH(0, -1, mm_init_cnsts, P.g_init_c, kBlock, d, static_cast<uint32_t*>(nullptr), prec);
-  LAUNCH(1, -1, mm_init_vars, grid_for(d.nV, kBlock), kBlock, d, int(P.mode.rec16()));
+  LAUNCH(0, -1, mm_init_cnsts, P.g_init_c, kBlock, d, static_cast<uint32_t*>(nullptr), prec, kwmm);
+  // (with the key window's choice and the alive constraints' keys in it: key_window_pass)
+  LAUNCH(1, -1, mm_init_vars, grid_for(d.nV, kBlock), kBlock, d, int(P.mode.rec16()), static_cast<const double*>(kwmm),
+         P.g_init_c, P.key_headroom);
   LAUNCH(1, -1, mm_clist, std::min(P.g_c, 2 * c->n_cu), kBlock, d, 1);
   HIPCHK(hipMemsetAsync(d.chgbits, 0, sizeof(uint64_t) * ((d.nC + 127) / 128 * 2 + 2), c->stream));
   // Host view of the sizes (upper bounds: rows and constraints only leave), refreshed at every poll; they
@@ -261,6 +278,8 @@ int solve_maxmin(lmmhip_ctx* c, double prec) {
     LAUNCH(4, r, P.saturate, int(P.cap_sat > 0 && gS > P.cap_sat ? P.cap_sat : gS), kBlock, d, int(r),
            P.mode.rdq() ? P.g_upd : gL);
     LAUNCH(5, r, P.update, P.g_upd, kBlock, d, int(r), prec);
+    if (c->profiling && c->vote_diag)  // measurement: the keys this update stored, and those at the window's top
+      LAUNCH(7, r, mm_key_diag, P.g_c, kBlock, d, int(r));
     return 0;
   };
   // the termination test, then the alive-constraint list and the alive-row compaction, at the end of a chunk (their
@@ -385,7 +404,7 @@ int solve_maxmin_frontier(lmmhip_ctx* c, double prec) {
     c->frontier.map_ok = true;
   }
   const FrontierPlan P = frontier_plan(c, d);
-  LAUNCH(0, -1, mm_init_cnsts, grid_for(d.nC, kBlock / kWave), kBlock, d, d.key32, prec);
+  LAUNCH(0, -1, mm_init_cnsts, grid_for(d.nC, kBlock / kWave), kBlock, d, d.key32, prec, static_cast<double*>(nullptr));
   LAUNCH(1, -1, fr_init_vars, grid_for(std::max<int64_t>(std::max<int64_t>(d.nV, d.nC), d.nnz / 4), kBlock), kBlock, d);
   auto round_launches = [&](int64_t r) -> int {
     if (r == 0) {

@@ -37,9 +37,11 @@ namespace lmmdev {
 // One group of kInitG lanes per constraint (kWave / kInitG constraints per wave at a time: a wave used to take its
 // ~120 constraints of C2 one after the other, each a dependent chain of loads — 377 us per solve).
 // key32: the frontier engine's 32-bit keys (FrFields::key32), written beside the 16-bit ones; null for the others.
+// The 16-bit keys are written in the legacy window; rlo / rhi: the lane's minimum and maximum over the ratios of the
+// constraints it made alive, from which the round engine chooses the solve's window (key_window_pass).
 constexpr int kInitG = 16;
 __device__ __forceinline__ int init_cnsts_waves(const Dev& s, uint32_t* key32, double prec, int64_t wave,
-                                                int64_t nwaves) {
+                                                int64_t nwaves, double& rlo, double& rhi) {
   const int lane = threadIdx.x & (kWave - 1), gl = lane & (kInitG - 1);
   constexpr int kGpw = kWave / kInitG;
   int alive_cnt = 0;
@@ -83,9 +85,11 @@ __device__ __forceinline__ int init_cnsts_waves(const Dev& s, uint32_t* key32, d
       s.cexp[c] = cexp_pack(alive ? dec_scale(bound) : 0, alive ? dec_scale(usage) : 0, fat, !alive);
       s.nvote[c] = int32_t(e - b);  // no element votes yet
       s.chg[c] = uint16_t(0xFFFF);
-      s.key[c] = alive ? ratio_key(r) : uint16_t(kDeadKey);
+      s.key[c] = alive ? ratio_key(r, kKeyWinLegacy) : uint16_t(kDeadKey);
       if (key32)
         key32[c] = alive ? ratio_key32(r) : kDead32;
+      rlo = alive ? fmin(rlo, r) : rlo;
+      rhi = alive ? fmax(rhi, r) : rhi;
       alive_cnt += alive;
     }
   }
@@ -95,9 +99,68 @@ __device__ __forceinline__ int init_cnsts_waves(const Dev& s, uint32_t* key32, d
 // (Round 6: the per-wave count of alive constraints this kernel used to add into one control word — read by nobody —
 // was 8,192 atomics on one address per solve, serialised in the memory-side unit after the grid's short work: the
 // whole 74-us init of C4 and ~70 us of C2's.)
-__global__ void __launch_bounds__(kBlock) mm_init_cnsts(Dev s, uint32_t* key32, double prec) {
+// kwmm (the round engine under LMMHIP_KEY_WINDOW; else null): [2 x gridDim.x] the minimum and maximum initial alive ratio
+// of each workgroup's constraints, (+inf, 0) where it made none alive — plain stores to the workgroup's own slots.
+__global__ void __launch_bounds__(kBlock) mm_init_cnsts(Dev s, uint32_t* key32, double prec, double* kwmm) {
   const int64_t wave = (int64_t(blockIdx.x) * kBlock + threadIdx.x) / kWave;
-  init_cnsts_waves(s, key32, prec, wave, int64_t(gridDim.x) * (kBlock / kWave));
+  double lo = dinf(), hi = 0.0;
+  init_cnsts_waves(s, key32, prec, wave, int64_t(gridDim.x) * (kBlock / kWave), lo, hi);
+  if (kwmm) {  // (uniform)
+    __shared__ double wlo[kBlock / kWave], whi[kBlock / kWave];
+    lo = wave_min(lo);
+    hi = wave_max(hi);
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+      wlo[threadIdx.x / kWave] = lo;
+      whi[threadIdx.x / kWave] = hi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int k = 1; k < kBlock / kWave; k++) {
+        lo = fmin(lo, wlo[k]);
+        hi = fmax(hi, whi[k]);
+      }
+      kwmm[2 * blockIdx.x] = lo;
+      kwmm[2 * blockIdx.x + 1] = hi;
+    }
+  }
+}
+
+// The round engine's key window of this solve (lmm_keywin.hpp), chosen on the device behind mm_init_cnsts (part of
+// mm_init_vars: no launch of its own): every workgroup reduces the init's per-workgroup extremes (nslots pairs, at most
+// kMaxBlocks: 32 KB out of the L2) to the same window, workgroup 0 writes it to the control words for the round
+// kernels, and the grid rewrites the 16-bit keys of the alive constraints — written in the legacy window by the init —
+// in it.  kwmm null (LMMHIP_KEY_WINDOW=0): the legacy window to the control words, the keys stay.
+__device__ __forceinline__ void key_window_pass(const Dev& s, const double* kwmm, int nslots, double headroom) {
+  KeyWin kw = kKeyWinLegacy;
+  if (kwmm) {
+    __shared__ double wlo[kBlock / kWave], whi[kBlock / kWave];
+    double lo = dinf(), hi = 0.0;
+    for (int i = threadIdx.x; i < nslots; i += kBlock) {
+      lo = fmin(lo, kwmm[2 * i]);
+      hi = fmax(hi, kwmm[2 * i + 1]);
+    }
+    lo = wave_min(lo);
+    hi = wave_max(hi);
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+      wlo[threadIdx.x / kWave] = lo;
+      whi[threadIdx.x / kWave] = hi;
+    }
+    __syncthreads();
+    for (int k = 0; k < kBlock / kWave; k++) {  // (every thread: the same values in the same order)
+      lo = fmin(lo, wlo[k]);
+      hi = fmax(hi, whi[k]);
+    }
+    kw = key_window(lo, hi, headroom);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    s.ctl[CTL_KW_BASE] = int32_t(kw.base);
+    s.ctl[CTL_KW_SHIFT] = kw.shift;
+  }
+  if (!kwmm)
+    return;
+  for (int64_t c = int64_t(blockIdx.x) * kBlock + threadIdx.x; c < s.nC; c += int64_t(gridDim.x) * kBlock)
+    if (!key_dead(s.key[c]))
+      s.key[c] = ratio_key(s.cst[c].ratio, kw);
 }
 
 // F: also the packed row records of buffer 0 in that form (the multi-launch engine's init only; Rec8: where the solve
@@ -119,7 +182,9 @@ __device__ __forceinline__ void init_vars_range(const Dev& s, int64_t t, int64_t
 
 // rec16: the solve's RowForm is Rec16, whose records need no sentinel behind the last row.  (An int, not the RowForm: a
 // compare with Rec16 instead of with zero is another instruction, and the mode types came in without moving any.)
-__global__ void __launch_bounds__(kBlock) mm_init_vars(Dev s, int rec16) {
+__global__ void __launch_bounds__(kBlock) mm_init_vars(Dev s, int rec16, const double* kwmm, int nslots,
+                                                       double headroom) {
+  key_window_pass(s, kwmm, nslots, headroom);
   const int64_t t = int64_t(blockIdx.x) * kBlock + threadIdx.x, nthreads = int64_t(gridDim.x) * kBlock;
   if (rec16)
     init_vars_range<RowForm::Rec16>(s, t, nthreads);
@@ -192,11 +257,16 @@ __device__ __forceinline__ void rdq_flush_lds(const Dev& s, int qround, RdqLds* 
     s.rdq[q][L->base + i] = L->buf[i];
 }
 
-__device__ __forceinline__ unsigned row_floor(unsigned sk, unsigned mk, double vb, double p) {
-  unsigned fl = sk;
-  if (vb > 0)
-    fl = min(fl, (unsigned)ratio_key(vb * p));
+// (kb: the key of the level bound * penalty in the solve's window, kDeadKey for an unbounded variable)
+__device__ __forceinline__ unsigned row_floor(unsigned sk, unsigned mk, unsigned kb) {
+  const unsigned fl = min(sk, kb);
   return fl <= mk ? 0u : fl;
+}
+// The key decides unless it ties, for the bound level too: kb < mk -> bound * penalty is below every ratio of the row,
+// the variable is fixed at its bound without a ratio load; kb > mk -> it is not, and the exact ratios are needed only
+// to break a tie among the constraints at the minimal key; kb == mk -> the exact compare.
+__device__ __forceinline__ unsigned bound_key(double vb, double p, KeyWin kw) {
+  return vb > 0 ? unsigned(ratio_key(vb * p, kw)) : kDeadKey;
 }
 
 // FATPIPE constraints (maxmin.cpp:625-658): usage = max of w/p over the unfixed elements.  A fixed element
@@ -231,6 +301,7 @@ template <int G> __global__ void __launch_bounds__(kBlock) mm_vote(Dev s, int ro
   if (s.ctl[CTL_DONE])  // light table empty (maxmin.cpp:680), detected by mm_done
     return;
   const int buf = s.ctl[CTL_BUF];
+  const KeyWin kw = key_win_ctl(s.ctl);
   __shared__ int st_rows, st_elems;  // profiling counters (LDS, one store per block)
   if (s.vstat && threadIdx.x == 0)
     st_rows = st_elems = 0;
@@ -301,8 +372,11 @@ template <int G> __global__ void __launch_bounds__(kBlock) mm_vote(Dev s, int ro
       nmin = grp_isum<G>(nmin);
       const double vb = need ? s.vbound[v] : -1.0;
       const bool live = need && !key_dead(mk);
+      const double p = need ? s.pen[v] : 1.0;
+      const unsigned kb = live ? bound_key(vb, p, kw) : kDeadKey;  // (group-uniform)
+      const bool bfix = kb < mk;
       double minr = dinf();
-      if (live && (nmin > 1 || vb > 0)) {
+      if (live && ((nmin > 1 && !bfix) || kb == mk)) {
         if (h0 && k0 == mk)
           minr = s.cst[c0].ratio;
         for (uint32_t j = j0 + G; j < e; j += G) {
@@ -312,8 +386,7 @@ template <int G> __global__ void __launch_bounds__(kBlock) mm_vote(Dev s, int ro
         }
       }
       minr = grp_min<G>(minr);
-      const double p = need ? s.pen[v] : 1.0;
-      const bool bounded = live && vb > 0 && vb * p < minr;
+      const bool bounded = live && (bfix || (kb == mk && vb * p < minr));
       int newt = INT_MAX;
       if (live && !bounded) {
         if (h0 && k0 == mk && (nmin == 1 || s.cst[c0].ratio == minr))
@@ -333,7 +406,7 @@ template <int G> __global__ void __launch_bounds__(kBlock) mm_vote(Dev s, int ro
       }
       sk = grp_umin<G>(sk);
       if (live && !bounded && g == 0)  // the row's floor, 0 = "sensitive" (see vote_row)
-        s.skey[buf][row] = uint16_t(row_floor(sk, mk, vb, p));
+        s.skey[buf][row] = uint16_t(row_floor(sk, mk, kb));
       int mult_new = h0 && c0 == newt, mult_old = h0 && c0 == t;
       for (uint32_t j = j0 + G; j < e; j += G) {
         const int32_t c = ccol[j];
@@ -466,8 +539,8 @@ constexpr int kFilt = LMM_KFILT;  // rows per lane per filter step (their loads 
 // from the original CSR whatever the buffer (the compaction moves the per-row words only, cmp_write_rows).
 template <int R, int M>
 __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64_t row, int* st_rows,
-                                         int* st_elems, const uint16_t* __restrict__ key, int* rdq_c = nullptr,
-                                         Anat an = Anat()) {
+                                         int* st_elems, const uint16_t* __restrict__ key, KeyWin kw,
+                                         int* rdq_c = nullptr, Anat an = Anat()) {
   static_assert(vote_mode_ok(M), "not one of the nine vote modes");
   constexpr VoteMode vm = vote_mode(M);
   an.restart();
@@ -561,8 +634,14 @@ __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64
     if (k == mk)
       newt = min(newt, c);
   }
+  // (bound_keys(): the bound level's key decides unless it ties, see bound_key; else every bounded variable takes the
+  // exact pass — the same decisions)
+  constexpr bool kBk = vm.bound_keys();
+  const unsigned kb = kBk ? bound_key(vb, p, kw) : kDeadKey;
+  const bool bfix = kBk && kb < mk;  // bound * penalty below every ratio of the row
   double minr = dinf();
-  if (nmin > 1 || vb > 0) {  // exact ratios at the minimal key: lexicographic min of (ratio, id)
+  if (kBk ? (nmin > 1 && !bfix) || kb == mk : nmin > 1 || vb > 0) {  // exact ratios at the minimal key: lexicographic
+                                                                     // min of (ratio, id)
     newt = INT_MAX;
     // the tied constraints' ratios: all loads issued before the first compare (one dependent level: a compare right
     // after each conditional load waits for the loads one at a time).  Not in the Arrays mode: the persistent
@@ -595,7 +674,7 @@ __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64
     }
   }
   an.level(4, minr + double(newt));
-  if (vb > 0 && vb * p < minr) {  // fixed at its bound (maxmin.cpp:587-589)
+  if (bfix || ((kBk ? kb == mk : vb > 0) && vb * p < minr)) {  // fixed at its bound (maxmin.cpp:587-589)
     s.vstate[v] = round + 1;  // fixed / dropped in this round
     s.x[v] = vb;
     rtgt[row] = kRetired;
@@ -621,7 +700,7 @@ __device__ __forceinline__ void vote_row(const Dev& s, int buf, int round, int64
       sk = min(sk, k);
     mult_new += c == newt;
   }
-  skey[row] = uint16_t(row_floor(sk, mk, vb, p));
+  skey[row] = uint16_t(row_floor(sk, mk, kBk ? kb : bound_key(vb, p, kw)));
   if (newt == t)
     return;
   if (t >= 0 && !key_dead(kt))
@@ -674,8 +753,8 @@ __device__ __forceinline__ void vote_wave_range(int64_t lo, int64_t hi, int64_t&
 template <bool kBits, int R, int F, int kDiag, int M>
 __device__ __forceinline__ int vote_waves(const Dev& s, int buf, int round, int64_t lo, int64_t hi,
                                           const uint64_t* bits, int* qw, int* st_rows, int* st_elems,
-                                          const uint16_t* __restrict__ key, RdqLds* rql = nullptr, Anat an = Anat(),
-                                          Anat ar = Anat()) {
+                                          const uint16_t* __restrict__ key, KeyWin kw, RdqLds* rql = nullptr,
+                                          Anat an = Anat(), Anat ar = Anat()) {
   constexpr VoteMode vm = vote_mode(M);
   const int lane = threadIdx.x & (kWave - 1);
   int64_t wlo, whi;
@@ -767,7 +846,7 @@ __device__ __forceinline__ int vote_waves(const Dev& s, int buf, int round, int6
         an.restart();
         an.count(1);
         if (kDiag == 0)
-          vote_row<R, M>(s, buf, round, row, st_rows, st_elems, key, &pc, ar);
+          vote_row<R, M>(s, buf, round, row, st_rows, st_elems, key, kw, &pc, ar);
         if (vm.rdq() && kDiag == 0)
           rdq_push_lds(s, pc, round, rql);
         an.level(8, 0u);
@@ -781,7 +860,7 @@ __device__ __forceinline__ int vote_waves(const Dev& s, int buf, int round, int6
   }
   int pc = -1;
   if (kDiag == 0 && lane < qn)
-    vote_row<R, M>(s, buf, round, qw[lane], st_rows, st_elems, key, &pc, ar);
+    vote_row<R, M>(s, buf, round, qw[lane], st_rows, st_elems, key, kw, &pc, ar);
   if (vm.rdq() && kDiag == 0)
     rdq_push_lds(s, pc, round, rql);
   if (an.on() && qn > 0)
@@ -907,7 +986,7 @@ __global__ void __launch_bounds__(vote_block(V)) mm_vote_lane(Dev s, int round) 
   int nq = 0;
   if (lo < hi)
     nq = vote_waves<kBits, 8, kFilt, kDiag, M>(s, buf, round, lo, hi, bits, q + (threadIdx.x / kWave) * kQW, &st_rows,
-                                               &st_elems, s.key, &rql, an, ar);
+                                               &st_elems, s.key, key_win_ctl(s.ctl), &rql, an, ar);
   if (kRdq && kDiag == 0)
     rdq_flush_lds(s, round, &rql);
   if (an.on()) {  // the wave's record (vote_row's levels: the slowest lane of the wave)
@@ -1479,7 +1558,8 @@ __device__ __forceinline__ void wave_lds_sync() {
 }
 template <int K, int U>  // U: the update mode's index (lmm_round_mode.hpp)
 __device__ __forceinline__ int update_groups(const Dev& s, int64_t wbase, int64_t stride, int round, double prec,
-                                             bool* touch, int* ucnt_sh = nullptr, int32_t* ulist = nullptr,
+                                             bool* touch, const int32_t* kwc, int* ucnt_sh = nullptr,
+                                             int32_t* ulist = nullptr,
                                              Anat an = Anat(), UpdQuadLds<K>* ql = nullptr) {
   static_assert(upd_mode_ok(U), "not an update mode");
   constexpr bool kRdq = upd_mode(U).rdq(), kQuad = upd_mode(U).quad();
@@ -1684,7 +1764,9 @@ __device__ __forceinline__ int update_groups(const Dev& s, int64_t wbase, int64_
             rec->ratio = r;
           else
             wq = r;
-          const unsigned nk = ratio_key(r);
+          // (kwc: the control words of a round-engine solve, whose window is read here, where a key is made — held
+          // from the kernel's start its two scalars cost mm_update<quad> two spilled VGPRs; null: the legacy window)
+          const unsigned nk = ratio_key(r, kwc ? key_win_ctl(kwc) : kKeyWinLegacy);
           s.key[c] = uint16_t(nk);
           changed = nk != okey[k];
           alive++;
@@ -1762,7 +1844,7 @@ __global__ void __launch_bounds__(kBlock, upd_mode(U).quad() ? 4 : 1) mm_update(
   const int64_t stride = int64_t(gridDim.x) * kBlock;
   for (int64_t base = (int64_t(blockIdx.x) * kBlock + threadIdx.x) & ~int64_t(kWave - 1); base < s.nC;
        base += LMM_UPD_K * stride)  // wave-uniform; LMM_UPD_K groups of 64 constraints per step, loads in flight together
-    alive += update_groups<LMM_UPD_K, U>(s, base, stride, round, prec, &any_touch, &ucnt_sh, ulist, an, ql);
+    alive += update_groups<LMM_UPD_K, U>(s, base, stride, round, prec, &any_touch, s.ctl, &ucnt_sh, ulist, an, ql);
   const unsigned long long t_loop = an.now();
   if (alive)
     atomicAdd(&alive_cnt, alive);
@@ -1787,6 +1869,28 @@ __global__ void __launch_bounds__(kBlock, upd_mode(U).quad() ? 4 : 1) mm_update(
       an.put(4 + f, an.lv(f));
     an.put(7, an.cnt(0));
     an.put(8, an.cnt(1));
+  }
+}
+
+// Key-window diagnostics (measurement only, LMMHIP_VOTE_DIAG under profiling), behind a round's update: the keys that
+// update stored (the alive constraints stamped with this round) and those of them at the window's top code, summed
+// over the solve in the control words (lmmhip_key_window).
+__global__ void __launch_bounds__(kBlock) mm_key_diag(Dev s, int round) {
+  if (s.ctl[CTL_DONE])
+    return;
+  int n = 0, nt = 0;
+  for (int64_t c = int64_t(blockIdx.x) * kBlock + threadIdx.x; c < s.nC; c += int64_t(gridDim.x) * kBlock) {
+    const unsigned k = s.key[c];
+    const bool st = !key_dead(k) && s.chg[c] == uint16_t(round);
+    n += st;
+    nt += st && k == kKeyTop;
+  }
+  n = grp_isum<kWave>(n);
+  nt = grp_isum<kWave>(nt);
+  if ((threadIdx.x & (kWave - 1)) == 0 && n) {
+    atomicAdd(&s.ctl[CTL_KW_STORES], n);
+    if (nt)
+      atomicAdd(&s.ctl[CTL_KW_CLAMP], nt);
   }
 }
 

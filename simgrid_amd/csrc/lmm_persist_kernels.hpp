@@ -216,7 +216,8 @@ __device__ void p_vote(const Dev& s, int buf, int round, int64_t nrows, PVoteLds
   int nq = 0;
   if (lo < hi)
     nq = vote_waves<kBits, R, kPFilt, 0, kVoteArrays>(s, buf, round, lo, hi, L.bits,
-                                                      L.q + (threadIdx.x / kWave) * kQW, &L.st0, &L.st1, s.key);
+                                                      L.q + (threadIdx.x / kWave) * kQW, &L.st0, &L.st1, s.key,
+                                                      kKeyWinLegacy);
   if (count) {  // (profiling) one add per workgroup: a per-wave add to one word cost ~6 us per round on C4
     if ((threadIdx.x & (kWave - 1)) == 0 && nq)
       atomicAdd(&L.st0, nq);
@@ -342,7 +343,10 @@ __global__ void __launch_bounds__(kPB) mm_persist(Dev s, unsigned* barw, double 
   if (!bar_rdv(b, rdv_ticks, hflag))
     return;
   unsigned gen = 0;
-  init_cnsts_waves(s, nullptr, prec, pwave(), int64_t(gridDim.x) * kPW);  // init (maxmin.cpp:509-555)
+  {
+    double rlo = dinf(), rhi = 0.0;  // (the round engine's key window: not used here)
+    init_cnsts_waves(s, nullptr, prec, pwave(), int64_t(gridDim.x) * kPW, rlo, rhi);  // init (maxmin.cpp:509-555)
+  }
   init_vars_range<RowForm::Arrays>(s, int64_t(blockIdx.x) * kPB + threadIdx.x, int64_t(gridDim.x) * kPB);
   if (!grid_sync(b, ++gen))
     return;
@@ -369,7 +373,7 @@ __global__ void __launch_bounds__(kPB) mm_persist(Dev s, unsigned* barw, double 
       constexpr int kU = 3;  // groups of 64 constraints per wave step, loads in flight together
       const int64_t stride = int64_t(gridDim.x) * kPB;
       for (int64_t base = pwave() * kWave; base < s.nC; base += kU * stride)  // wave-uniform
-        alive += update_groups<kU, kUpdPlain>(s, base, stride, r, prec, &touch);
+        alive += update_groups<kU, kUpdPlain>(s, base, stride, r, prec, &touch, nullptr);
       alive = grp_isum<kWave>(alive);
       if (lane == 0 && alive)
         atomicAdd(&L.cnt, alive);

@@ -34,6 +34,9 @@ struct VoteMode {
   // the tied constraints' exact ratios loaded together (vote_row): the record forms, which only the round engine's
   // short-row vote runs.  Arrays — the round engine without records, the persistent kernel — keeps its registers.
   constexpr bool tie_loads() const { return rec(); }
+  // a bounded variable's level bound * penalty compared by its key first, the exact ratios read only where the keys tie
+  // (vote_row): the record forms again — in the persistent kernel the key's register spilled 39 VGPRs
+  constexpr bool bound_keys() const { return rec(); }
   constexpr bool valid() const { return rec() || (!queue && !filter); }
   constexpr int index() const { return !rec() ? 0 : 1 + 4 * int(rec16()) + 2 * int(queue) + int(filter); }
 };

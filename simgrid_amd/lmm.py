@@ -190,6 +190,7 @@ SIGNATURES = {
     "lmmhip_ctx_use_own_stream": (I, [P]),
     "lmmhip_ctx_set_engine": (I, [P, I]),
     "lmmhip_engine_fallbacks": (I, [P, PI64]),
+    "lmmhip_key_window": (I, [P, PI64]),
     "lmmhip_last_engine": (I, [P, PI]),
     "lmmhip_persist_profile": (I, [P, I, PI64, I64, PI64]),
     "lmmhip_persist_profile_blocks": (I, [P, PI64, I64, PI64, PI64]),
@@ -567,6 +568,13 @@ class System:
         n = ct.c_int64()
         _check_hip(lib().lmmhip_engine_fallbacks(self.device_ctx(), ct.byref(n)))
         return n.value
+
+    def key_window(self):
+        """The round engine's key window of the last solve (lmmhip_key_window): base, shift, and — after a profiled
+        solve — the keys the updates stored and those of them that clamped at the window's top."""
+        out = (ct.c_int64 * 4)()
+        _check_hip(lib().lmmhip_key_window(self.device_ctx(), out))
+        return dict(base=out[0], shift=out[1], key_stores=out[2], key_clamped=out[3])
 
     # lmmhip_last_engine's answers (include/lmm/lmm_hip.h, LMMHIP_RAN_*)
     RAN_PERSISTENT, RAN_ROUNDS, RAN_FRONTIER, RAN_BATCH, RAN_FB_ROUNDS, RAN_FB_BATCH = range(6)
